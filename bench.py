@@ -17,6 +17,15 @@ N*m points is assembled on every rank by one all_gather per step.  The same JSON
 workload as `c3_sharded`: LML + gradient over 64 settings at n = 4096 sharded 64/N per GPU (strong scaling, settings/s, per-rank
 seconds, and the C-ABI's own RCCL path gp_dist_lml_grad_batched checked against it).
 torch is used for rendezvous/barrier/max-reduce only; all compute goes through libgpcore.so.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: set up, warm up, time the K steps
+and print the result line (metric, value, unit, ms_per_step, ...).  `--full` adds everything else the line used to carry, as it was:
+the MFMA probe, HIP events per kernel class during the timed steps (`roofline`, `gram`), the stage breakdown and the look-ahead-off
+refit (`cholesky`), the end-to-end step with transfers, `c3_sharded`, PMC traffic from profiles/, and the two CPU baselines with their
+comparison against the GPU result (`--no-cpu-baseline`, `--no-c3`, `--cpu-fit-full` act under `--full` only).  `--workload c3|c4|c5`
+are explicit requests for another configuration and run as a whole with or without `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (C2: `mean.npy`, `var.npy`, and `lml.npy` of the refit) as float64
+.npy files, at most 64 MB in all; the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -33,6 +42,35 @@ if ROOT not in sys.path:
 
 PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X vendor fp64 matrix peak; the probe value is printed next to it
 PEAK_HBM_GBS = 8000.0
+
+
+def ensure_built():
+    """The benchmark may run as a user who cannot write into the tree (somebody else checked it out and ran build()), and build()
+    opens its lock file for writing before it looks at anything.  So: a library that is there and newer than its sources is
+    loaded as it is; only a missing or stale one goes to build(), whose error then says what is wrong."""
+    import __graft_entry__ as entry
+    stale = getattr(entry, "_stale", None)
+    if stale is None or stale(entry.LIB, entry.SRC + entry.HDR):
+        entry.build()
+    from gp_algos_amd import _lib
+    _lib.load()
+
+
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: DIR/<name>.npy (float64) for every array the last timed step produced.  All files together stay within
+    DUMP_BYTES_MAX: an array over its equal share of that is cut to a sample of its flattened elements, the indices drawn without
+    replacement by a generator seeded with 0 and sorted -- the same elements in every run of the same command."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(len(arrays), 1) - 4096          # (the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 8, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def progress(msg):
@@ -215,8 +253,7 @@ def run_secondary(args):
     backend = os.environ.get("GPCORE_BENCH_BACKEND", "nccl")
     gdist.init(backend, torch.device("cuda", local_rank))
     coll_dev = "cuda" if backend == "nccl" else "cpu"
-    import __graft_entry__ as entry
-    entry.build()
+    ensure_built()
     from gp_algos_amd import _lib as L, synth
     from gp_algos_amd.core import Context, EpClassifierState
     ctx = Context(local_rank)
@@ -233,6 +270,8 @@ def run_secondary(args):
         n = args.n if args.n != 8192 else 4096
         c3 = measure_c3(ctx, n, args.d, args.steps, args.warmup, rank, world, local_rank, backend, coll_dev, names)
         xin = c3.pop("_cross_check_inputs")
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"lml": xin[1], "grad": xin[2]})
         if rank == 0:
             P, B = args.d + 2, c3["B"]
             print(json.dumps({"metric": "LML+gradient settings/sec at n=%d fp64, P=%d" % (n, P), "value": c3["settings_per_s"],
@@ -292,6 +331,8 @@ def run_secondary(args):
             # n / 128 steps of a full batch (the PMC passes ran full batches of 131072 rows)
             mb = min(m, 131072)
             roof["algorithmic_bytes_per_launch"] = 8.0 * (mb * ((n + 128) / 2.0) + 128 * ((n + 128) / 2.0) + mb * 128)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"mean": full[:, 0], "var": full[:, 1]})
         if rank == 0:
             var = full[:, 1]
             print(json.dumps({"metric": "posterior variances/sec at n=%d fp64 (L resident)" % n, "value": m_total * args.steps / dt,
@@ -327,6 +368,8 @@ def run_secondary(args):
         fence()
         progress("c4: fence after the timed sweeps passed")
         dt = gdist.max_over_ranks(time.perf_counter() - t0, device=coll_dev)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tau": tau, "nu": nu})
         # the roofline block's HIP events (two per launch of the profiled classes, on four streams) cost this latency-bound workload
         # ~5 %: they are taken on ONE extra step after the timed ones.  --no-roofline-events leaves that step out (the roofline block
         # is then null): a rocprofv3 --pmc pass only needs the kernels to run, and the WRITE_SIZE pass of this workload stopped
@@ -601,18 +644,26 @@ def main():
     ap.add_argument("--train-n", dest="n", type=int, default=8192)
     ap.add_argument("--dim", dest="d", type=int, default=8)
     ap.add_argument("--test-points", dest="m", type=int, default=65536)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: besides the headline figure, everything else the line can carry: MFMA probe, per-kernel-class HIP events "
+                         "(roofline, gram), stage breakdown, look-ahead-off refit (cholesky), end-to-end step with transfers, c3_sharded, "
+                         "PMC traffic, CPU baselines and their comparison with the GPU result (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="c2 (default, the BASELINE.json metric): fit + posterior; c3: batched LML+gradient over 64 settings; "
                          "c4: EP classification sweeps; c5: n=32768 fit once, then 10^6/8 test-point variances per GPU per step")
     ap.add_argument("--dry-launch", action="store_true",
                     help="ranks print their RANK / LOCAL_RANK / WORLD_SIZE as one JSON line and exit without touching the GPU "
                          "(the launch path of --gpus N, testable on a host without a GPU)")
-    ap.add_argument("--cpu-fit-full", action="store_true", help="cpu_baseline: time the oracle's fit at the full n (about a minute)")
-    ap.add_argument("--no-c3", action="store_true", help="leave the c3_sharded block out of the c2 line")
+    ap.add_argument("--cpu-fit-full", action="store_true", help="--full, cpu_baseline: time the oracle's fit at the full n (about a minute)")
+    ap.add_argument("--no-c3", action="store_true", help="--full: leave the c3_sharded block out of the c2 line (c4: the ep_grid block)")
     ap.add_argument("--no-roofline-events", action="store_true",
                     help="c4: skip the extra step that records HIP events around every launch of the profiled classes (for rocprofv3 --pmc passes)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become one.  Nothing above this line imports torch or loads libgpcore.so.
         raise SystemExit(self_launch(args.gpus, sys.argv[1:], dry=args.dry_launch))
@@ -647,8 +698,7 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
 
-    import __graft_entry__ as entry
-    entry.build()
+    ensure_built()
     from gp_algos_amd import _lib as L, synth
     from gp_algos_amd.core import Context
 
@@ -661,7 +711,7 @@ def main():
 
     ctx = Context(local_rank)
     lib = ctx._lib
-    probe = ctx.probe_mfma_f64()
+    probe = ctx.probe_mfma_f64() if args.full else None
     dX, dy, dXs = ctx.upload(p["X"]), ctx.upload(p["y"]), ctx.upload(p["Xs"])
     gathered = None
     if world > 1 and backend == "nccl":
@@ -696,7 +746,8 @@ def main():
         step()
     fence()
     prof_mask = (1 << L.GP_PROF_GEMM) | (1 << L.GP_PROF_SYRK) | (1 << L.GP_PROF_GRAM)
-    ctx.profile(prof_mask)
+    if args.full:                       # HIP events around every launch of these classes: the roofline and gram blocks
+        ctx.profile(prof_mask)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -704,14 +755,58 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     ctx.profile(0)
-    g_k, g_ms, g_work = ctx.profile_read(L.GP_PROF_GEMM)
-    s_k, s_ms, s_work = ctx.profile_read(L.GP_PROF_SYRK)
-    r_k, r_ms, r_work = ctx.profile_read(L.GP_PROF_GRAM)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    ms_per_step = dt / args.steps * 1e3
+    value = world * m * args.steps / dt
 
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the posterior of the test points (of all N m points where they
+        # are assembled on every rank, rank by rank) and the LML of the refit
+        if gathered is not None:
+            post = gathered.cpu().numpy().reshape(world, 2, m)
+            omean, ovar = post[:, 0, :].ravel(), post[:, 1, :].ravel()
+        else:
+            omean, ovar = ctx.download(dmean, (m,)), ctx.download(dvar, (m,))
+        olml = np.zeros(1)
+        ctx.check(lib.gp_model_get(h, L.GP_GET_LML, L.dptr(olml), 1))
+        dump_outputs(args.dump_outputs, {"mean": omean, "var": ovar, "lml": olml})
+
+    head = None
+    if rank == 0:
+        head = {
+            "metric": "GP posterior (mu,var) points/sec at n=%d fp64 (fit + predict per step)" % n,
+            "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "C2: GP regression, ARD-RBF, n=%d d=%d fp64, Gram + Cholesky + posterior mean/variance at m=%d "
+                                   "test points per GPU" % (n, d, m), "n": n, "d": d, "m_per_gpu": m,
+                       "parallelism": ("test points sharded %d-way (m per GPU), model refit per rank; the posterior of all %d points is "
+                                       "assembled on every rank by one all_gather of 2 m doubles per rank per step (RCCL)" % (world, world * m))
+                       if gathered is not None else "single GPU" if world == 1 else
+                       "test points sharded %d-way, model refit per rank, results left on the rank (rehearsal backend)" % world,
+                       "timed_region": "X, y, X* resident in HBM before the timed steps; per step: Gram + Cholesky + alpha/LML refit, then mean "
+                                       "and variance of all m points, results left in HBM (H2D of X* = m*d*8 B and D2H of 2m doubles are outside "
+                                       "the timed region: 5 MB per step, DESIGN.md section 5)"},
+        }
+
+    def finish():
+        lib.gp_model_destroy(h)
+        ctx.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        return finish()
+
+    g_k, g_ms, g_work = ctx.profile_read(L.GP_PROF_GEMM)
+    s_k, s_ms, s_work = ctx.profile_read(L.GP_PROF_SYRK)
+    r_k, r_ms, r_work = ctx.profile_read(L.GP_PROF_GRAM)
     # stage breakdown (untimed, rank 0 only needs it)
     ctx.sync()
     t1 = time.perf_counter()
@@ -776,24 +871,10 @@ def main():
                 traffic = pm["kernels"][DOMINANT_KERNEL]["hbm_bytes_per_launch_corrected"]
         except Exception:
             traffic = None
-        ms_per_step = dt / args.steps * 1e3
-        value = world * m * args.steps / dt
         gemm_tflops = g_work / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
         syrk_tflops = s_work / (s_ms * 1e-3) / 1e12 if s_ms > 0 else 0.0
-        out = {
-            "metric": "GP posterior (mu,var) points/sec at n=%d fp64 (fit + predict per step)" % n,
-            "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C2: GP regression, ARD-RBF, n=%d d=%d fp64, Gram + Cholesky + posterior mean/variance at m=%d "
-                                   "test points per GPU" % (n, d, m), "n": n, "d": d, "m_per_gpu": m,
-                       "parallelism": ("test points sharded %d-way (m per GPU), model refit per rank; the posterior of all %d points is "
-                                       "assembled on every rank by one all_gather of 2 m doubles per rank per step (RCCL)" % (world, world * m))
-                       if gathered is not None else "single GPU" if world == 1 else
-                       "test points sharded %d-way, model refit per rank, results left on the rank (rehearsal backend)" % world,
-                       "timed_region": "X, y, X* resident in HBM before the timed steps; per step: Gram + Cholesky + alpha/LML refit, then mean "
-                                       "and variance of all m points, results left in HBM (H2D of X* = m*d*8 B and D2H of 2m doubles are outside "
-                                       "the timed region: 5 MB per step, DESIGN.md section 5)"},
+        out = dict(head)
+        out.update({
             "roofline": {"kernel": DOMINANT_KERNEL + " (posterior step Vt_i = Vt[:, :128(i+1)] Lw_i^T: update and panel solve of block "
                                    "column i in one product on 256x128 tiles, one 8-wave workgroup (64x64 per wave) per CU, row reductions in the "
                                    "epilogue; v_mfma_f64_16x16x4_f64)",
@@ -813,7 +894,7 @@ def main():
                         % ((hX.nbytes + hy.nbytes + hXs.nbytes) / 1e6, 2 * hmean.nbytes / 1e6),
             "mfma_f64_probe_tflops": probe,
             "c3_sharded": c3,
-        }
+        })
     # CPU baseline on rank 0 at N=1 only
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         Lh = np.zeros((n, n), order="F")
@@ -839,11 +920,7 @@ def main():
         # only now, with the line out: the C-ABI's own RCCL path against the torch.distributed result (stderr)
         c3["_cross_check_inputs"] = c3_inputs
         c_abi_cross_check(ctx, c3, rank, world, local_rank, backend)
-    lib.gp_model_destroy(h)
-    ctx.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

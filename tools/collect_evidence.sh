@@ -24,15 +24,15 @@ pmc() {   # pmc <name> <bench args...>: FETCH / WRITE / MFMA-busy passes of one 
     rm -rf $O/pmc_${name}_FETCH_SIZE $O/pmc_${name}_WRITE_SIZE $O/pmc_${name}_SQ_VALU_MFMA_BUSY_CYCLES
 }
 if [ $FROM -le 0 ]; then
-python3 $R/bench.py > $O/bench_c2.json 2> $O/bench_c2.err && say "c2 ok"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o c2 -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-c3 > $O/stats.log 2>&1 && say "stats ok"
+python3 $R/bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err && say "c2 ok"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o c2 -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-c3 > $O/stats.log 2>&1 && say "stats ok"
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/bench_c2_kernel_stats.csv 2>/dev/null; rm -rf $O/stats
 python3 $R/bench.py --workload c3 --steps 3 --warmup 1 > $O/bench_c3.json 2> $O/bench_c3.err && say "c3 ok"
 python3 $R/bench.py --workload c4 --steps 2 > $O/bench_c4.json 2> $O/bench_c4.err && say "c4 ok"
 python3 $R/bench.py --workload c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err && say "c5 ok"
 fi
 if [ $FROM -le 1 ] && [ -z "$SKIP_PMC" ]; then
-pmc c2 --steps 1 --warmup 1 --no-cpu-baseline --no-c3
+pmc c2 --full --steps 1 --warmup 1 --no-cpu-baseline --no-c3
 pmc c3 --workload c3 --steps 1 --warmup 1
 fi
 if [ $FROM -le 2 ] && [ -z "$SKIP_PMC" ]; then
