@@ -6,7 +6,8 @@
 2. oracle_vectors.json: small seeded problems with the CPU oracle's outputs (fit / predict / LML /
    gradient / EP).  The JVM reference cannot run here (no JDK), so these vectors are
    ORACLE-generated: they pin the oracle and the HIP path against regressions; parity against the JVM is
-   pinned only by the reference's own known-answer literals (tests/test_oracle_kat.py)."""
+   pinned only by the reference's own known-answer literals (tests/test_oracle_kat.py).
+What the right answer IS (40-digit values of SURVEY.md Appendix A, independent of the oracle) comes from make_truth.py beside this file."""
 import json
 import os
 import shutil

@@ -483,8 +483,9 @@ def test_ep_sweeps_vs_oracle(ctx, n, sweeps):
 @pytest.mark.parametrize("n,sweeps", [(130, 2), (300, 3), (700, 2)])
 def test_ep_block_kernel_forms_vs_oracle(ctx, monkeypatch, n, sweeps):
     """The block kernel (site loop of a block on one wave without barriers) with the link between two blocks as one launch or two
-    (GPCORE_EP_LINK), end-of-sweep refactorisation: against the oracle.  (The fused chain kernel of the streamed form has its own
-    test below, bit for bit against this one.)"""
+    (GPCORE_EP_LINK), end-of-sweep refactorisation: against the oracle.  (The fused chain kernel of the streamed form is compared with
+    the oracle state by state in test_ep_streamed_fused_default_vs_oracle below, and bit for bit with the block kernel + link kernel
+    of the same streamed form in test_ep_fused_chain_equals_block_and_link_kernels.)"""
     from gp_algos_amd import _lib as L
     from gp_algos_amd.core import EpClassifierState
     p, K, y = _ep_problem(n, seed=n + 3)
@@ -497,6 +498,60 @@ def test_ep_block_kernel_forms_vs_oracle(ctx, monkeypatch, n, sweeps):
         ep.close()
         for key, val in got.items():
             assert np.max(np.abs(val - o[key])) <= TOL_EP * np.max(np.abs(o[key])), (link, key)
+
+
+def test_ep_streamed_fused_default_vs_oracle(ctx):
+    """n = 1100 (np = 1152): the smallest padded size at which the refactorisation streamed under the site loop, the fused chain kernel
+    (ep_block2_kernel: fused link, urgent tiles, far split, four streams) is what runs with no environment set.  The whole state
+    after two sweeps against the oracle's literal loop (~4 n^3 flops per sweep: two is what a test can afford)."""
+    from gp_algos_amd import _lib as L
+    from gp_algos_amd.core import EpClassifierState
+    n, sweeps = 1100, 2
+    p, K, y = _ep_problem(n, seed=53)
+    o = orc.ep_estimate(K, y, sweeps)
+    ep = EpClassifierState(ctx, K, y)
+    tau, nu = ep.sweep(sweeps)
+    got = dict(tau=tau, nu=nu, mu=ep.get(L.GP_EP_GET_MU), Sigma=ep.get(L.GP_EP_GET_SIGMA), cav_tau=ep.get(L.GP_EP_GET_CAV_TAU), L=ep.get(L.GP_EP_GET_L))
+    for key, val in got.items():
+        assert np.max(np.abs(val - o[key])) <= TOL_EP * np.max(np.abs(o[key])), key
+    assert np.all(np.triu(got["L"], 1) == 0.0)
+    for strict in (True, False):
+        ol = orc.ep_lml(o, y, strict=strict)
+        assert abs(ep.lml(strict=strict) - ol) <= 1e-9 * max(1.0, abs(ol))
+    ep.close()
+
+
+def test_ep_fused_chain_equals_block_and_link_kernels(ctx, monkeypatch):
+    """Same problem, streamed refactorisation forced on: the fused chain kernel (GPCORE_EP_FUSED=1, the link of block b-1 as the
+    prologue of block b's kernel) against block kernel + link kernel (GPCORE_EP_FUSED=0) -- the same operations in the same order
+    per element, so the site parameters are the same bits (the claim in the comment at gp_ep_sweep's GPCORE_EP_FUSED)."""
+    from gp_algos_amd.core import EpClassifierState
+    _, K, y = _ep_problem(1100, seed=53)
+    monkeypatch.setenv("GPCORE_EP_PIPELINE", "1")
+    got = {}
+    for fused in ("1", "0"):
+        monkeypatch.setenv("GPCORE_EP_FUSED", fused)
+        ep = EpClassifierState(ctx, K, y)
+        got[fused] = ep.sweep(2)
+        ep.close()
+    d_tau, d_nu = np.max(np.abs(got["1"][0] - got["0"][0])), np.max(np.abs(got["1"][1] - got["0"][1]))
+    print("fused vs block + link: max|dtau| = %.3e  max|dnu| = %.3e" % (d_tau, d_nu))
+    assert np.array_equal(got["1"][0], got["0"][0]) and np.array_equal(got["1"][1], got["0"][1])
+
+
+def test_ep_50_sweeps_drift_vs_oracle(ctx):
+    """Fifty sweeps: rounding differences between the blocked form and the literal loop must not accumulate from sweep to sweep."""
+    from gp_algos_amd import _lib as L
+    from gp_algos_amd.core import EpClassifierState
+    _, K, y = _ep_problem(300, seed=59)
+    o = orc.ep_estimate(K, y, 50)
+    ep = EpClassifierState(ctx, K, y)
+    tau, nu = ep.sweep(50)
+    mu = ep.get(L.GP_EP_GET_MU)
+    ep.close()
+    assert o["sweeps"] == 50
+    for key, val in (("tau", tau), ("nu", nu), ("mu", mu)):
+        assert np.max(np.abs(val - o[key])) <= TOL_EP * np.max(np.abs(o[key])), key
 
 
 def test_ep_sweeps_one_at_a_time_equal_batched(ctx):
