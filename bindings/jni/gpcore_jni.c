@@ -383,6 +383,29 @@ JNIEXPORT void JNICALL Java_gpcore_Native_epPredict(JNIEnv *env, jclass k, jlong
     }
     free(P); free(KD); free(KS);
 }
+/* the classifier from data: K and K* are built on the device (gp_ep_create_rbf / gp_ep_predict_rbf) */
+JNIEXPORT jlong JNICALL Java_gpcore_Native_epCreateRbf(JNIEnv *env, jclass k, jlong h, jdoubleArray x, jint xoff, jint n, jint d, jint ldx,
+                                                       jintArray targets, jdoubleArray theta) {
+    double *X = in_d(env, x, xoff, span(n, d, ldx));
+    jint *Y = X ? in_i(env, targets, n) : NULL;
+    double *T = Y ? in_d(env, theta, 0, d + 2) : NULL;
+    gp_ep *ep = NULL;
+    if (T) {
+        gp_status st = gp_ep_create_rbf(CTX(h), X, n, d, ldx, (const int32_t *)Y, T, &ep);
+        if (st != GP_OK) { throw_for(env, CTX(h), st, 0); ep = NULL; }
+    }
+    free(T); free(Y); free(X);
+    return (jlong)(intptr_t)ep;
+}
+JNIEXPORT void JNICALL Java_gpcore_Native_epPredictRbf(JNIEnv *env, jclass k, jlong h, jlong e, jdoubleArray xs, jint off, jint m, jint d,
+                                                       jint ldxs, jdoubleArray prob) {
+    double *XS = in_d(env, xs, off, span(m, d, ldxs)), *P = XS ? out_d(env, m) : NULL;
+    if (P) {
+        gp_status st = gp_ep_predict_rbf(EP(e), XS, m, ldxs, P, NULL, NULL);
+        if (st != GP_OK) throw_for(env, CTX(h), st, 0); else put_d(env, prob, 0, P, m);
+    }
+    free(P); free(XS);
+}
 JNIEXPORT void JNICALL Java_gpcore_Native_epDestroy(JNIEnv *env, jclass k, jlong e) { gp_ep_destroy(EP(e)); }
 
 /* ---- EP hyper-parameter fitting (HyperParamsOptimization.scala:31-55) ---- */

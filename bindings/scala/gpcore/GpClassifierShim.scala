@@ -31,6 +31,37 @@ class GpClassifier(stopCriterion: EpParameterEstimator.stopCriterionFunc) {
       DenseVector(prob)
     } finally Native.epDestroy(ep)
   }
+
+  // The same (:24-47) from DATA with the ARD-RBF kernel at hyperParams, as the reference's callers build their matrices
+  // (CancerClassificationTest; MarginalLikelihoodEvaluator.scala:37): the train Gram and the test-train block are built on the
+  // device and never cross the boundary.  learnParams = None runs the sweeps under stopCriterion as trainClassifier does.
+  def classifyFromData(trainData: DenseMatrix[Double], targets: DenseVector[Int], hyperParams: KernelFuncHyperParams,
+                       testData: DenseMatrix[Double], learnParams: Option[learnParams] = None): classifyOut = {
+    require(trainData.rows == targets.length && trainData.cols == testData.cols)
+    val x = dense(trainData); val xs = dense(testData)
+    val n = x.rows; val m = xs.rows
+    val ep = Native.epCreateRbf(ctx, x.data, x.offset, n, x.cols, x.majorStride, targets.toArray, hyperParams.toDenseVector.toArray)
+    try {
+      learnParams match {
+        case Some((site, _)) =>
+          rethrowNotPd { Native.epSetSiteParams(ctx, ep, n, site.tauSiteParams.toArray, site.niSiteParams.toArray) }
+        case None =>
+          var current = SiteParams(DenseVector.zeros[Double](n), DenseVector.zeros[Double](n))
+          var old = current
+          var j = 0
+          while (j == 0 || !stopCriterion(EpParameterEstimator.EpEstimationContext(currentParams = current, oldParams = old))) {
+            old = current
+            val tau = new Array[Double](n); val nu = new Array[Double](n)
+            rethrowNotPd { Native.epSweep(ctx, ep, 1, n, tau, nu) }
+            current = SiteParams(DenseVector(tau), DenseVector(nu))
+            j += 1
+          }
+      }
+      val prob = new Array[Double](m)
+      Native.epPredictRbf(ctx, ep, xs.data, xs.offset, m, xs.cols, xs.majorStride, prob)
+      DenseVector(prob)
+    } finally Native.epDestroy(ep)
+  }
 }
 
 object GpClassifier {

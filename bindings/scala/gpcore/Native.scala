@@ -37,6 +37,8 @@ object Native {
   @native def epLmlGradRbf(ctx: Long, ep: Long, x: Array[Double], xoff: Int, n: Int, d: Int, ldx: Int, theta: Array[Double], strict: Boolean, grad: Array[Double]): Unit
   @native def epGet(ctx: Long, ep: Long, what: Int, out: Array[Double], ld: Int): Unit
   @native def epPredict(ctx: Long, ep: Long, ks: Array[Double], off: Int, m: Int, n: Int, ldks: Int, kssDiag: Array[Double], prob: Array[Double]): Unit
+  @native def epCreateRbf(ctx: Long, x: Array[Double], xoff: Int, n: Int, d: Int, ldx: Int, targets: Array[Int], theta: Array[Double]): Long
+  @native def epPredictRbf(ctx: Long, ep: Long, xs: Array[Double], off: Int, m: Int, d: Int, ldxs: Int, prob: Array[Double]): Unit
   @native def epDestroy(ep: Long): Unit
   @native def epOptimizeRbf(ctx: Long, x: Array[Double], xoff: Int, n: Int, d: Int, ldx: Int, y: Array[Int], thetaInOut: Array[Double], stopEps: Double, maxSweeps: Int, strict: Boolean, maxIter: Int, history: Int): Double
   // batched small-n posteriors: GPOptimizer (GP-UCB), GPUnscentedKalmanFilter (GP-UKF)

@@ -70,6 +70,9 @@ SIGNATURES = {
     "gp_ep_lml_grad_rbf": (_i, [_vp, _dp, _i, _i, _dp, _i, _dp]),
     "gp_ep_get": (_i, [_vp, _i, _dp, _i]),
     "gp_ep_predict": (_i, [_vp, _dp, _i, _i, _dp, _dp]),
+    "gp_ep_create_rbf": (_i, [_vp, _dp, _i, _i, _i, C.POINTER(C.c_int32), _dp, C.POINTER(_vp)]),
+    "gp_ep_predict_rbf": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp]),
+    "gp_ep_predict_rbf_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ep_lml_rbf_batched": (_i, [_vp, _dp, _i, _i, _i, C.POINTER(C.c_int32), _dp, _i, _d, _i, _i, _dp, _ip, _ip]),
     "gp_ep_lml_grad_rbf_batched": (_i, [_vp, _dp, _i, _i, _i, C.POINTER(C.c_int32), _dp, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
     "gp_ep_optimize_rbf": (_i, [_vp, _dp, _i, _i, _i, C.POINTER(C.c_int32), _dp, _d, _i, _i, _i, _i, _dp, _dp, _ip, _ip]),

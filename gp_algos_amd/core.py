@@ -564,6 +564,26 @@ class EpClassifierState:
         st = ctx._lib.gp_ep_create(ctx.h, L.dptr(K), self.n, self.n, y.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h))
         ctx.check(st)
         self.h = h
+        self.d = None
+
+    @classmethod
+    def from_inputs(cls, ctx, X, y, theta):
+        """gp_ep_create_rbf: the classifier from training DATA -- the Gram matrix of the ARD-RBF kernel at theta is built on the
+        device, X and theta stay with the state for predict_inputs."""
+        X, theta = L.f64(X), L.f64(theta)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if X.ndim != 2 or y.size != X.shape[0]:
+            raise ValueError("trainData.rows must equal targets.length")
+        n, d = X.shape
+        if theta.size != d + 2:
+            raise ValueError("%d does not equal to %d" % (theta.size, d + 2))
+        self = cls.__new__(cls)
+        self.ctx, self.n, self.d, self.h = ctx, n, d, None
+        h = C.c_void_p()
+        st = ctx._lib.gp_ep_create_rbf(ctx.h, L.dptr(X), n, d, max(n, 1), y.ctypes.data_as(C.POINTER(C.c_int32)), L.dptr(theta), C.byref(h))
+        ctx.check(st)
+        self.h = h
+        return self
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -571,6 +591,41 @@ class EpClassifierState:
         self.h = None
 
     __del__ = close
+
+    def predict_inputs(self, Xs, latent=False, batch_rows=0):
+        """GpClassifier.classify at the test points Xs (m x d) for a state from from_inputs: class-1 probabilities, or
+        (prob, fmean, fvar) with latent=True.  batch_rows != 0 takes the device-pointer entry (gp_ep_predict_rbf_dev) with that many
+        test points per batch; 0 the host entry with the default batch."""
+        Xs = L.f64(Xs)
+        if Xs.ndim != 2 or (self.d is not None and Xs.shape[1] != self.d):
+            raise ValueError("test data dimension mismatch")
+        batch_rows = int(batch_rows)
+        if batch_rows < 0:
+            raise ValueError("batch_rows < 0")
+        m = Xs.shape[0]
+        lib, ctx = self.ctx._lib, self.ctx
+        prob = np.zeros(m)
+        fmean, fvar = (np.zeros(m), np.zeros(m)) if latent else (None, None)
+        if batch_rows == 0 or m == 0:
+            ctx.check(lib.gp_ep_predict_rbf(self.h, L.dptr(Xs), m, max(m, 1), L.dptr(prob), L.dptr(fmean) if latent else None,
+                                            L.dptr(fvar) if latent else None))
+        else:
+            dXs = ctx.upload(Xs)
+            dout = None
+            try:
+                dout = ctx.dev_alloc(3 * m * 8)
+                dp = lambda k: C.c_void_p(dout.value + k * m * 8)
+                ctx.check(lib.gp_ep_predict_rbf_dev(self.h, dXs, m, m, batch_rows, dp(0), dp(1) if latent else None, dp(2) if latent else None))
+                ctx.sync()
+                out = ctx.download(dout, (m, 3 if latent else 1))
+                prob = np.ascontiguousarray(out[:, 0])
+                if latent:
+                    fmean, fvar = np.ascontiguousarray(out[:, 1]), np.ascontiguousarray(out[:, 2])
+            finally:
+                ctx.dev_free(dXs)
+                if dout is not None:
+                    ctx.dev_free(dout)
+        return (prob, fmean, fvar) if latent else prob
 
     def sweep(self, nsweeps=1):
         tau, nu = np.zeros(self.n), np.zeros(self.n)

@@ -776,7 +776,9 @@ void gpi_chol_panel_step(gp_ctx *ctx, hipStream_t s, double *A, int np, int lda,
     gp_prof_end(ctx, GP_PROF_SYRK, count * trapezoid_flops(rows - c1, near, wcols), s);
 }
 void gpi_solve_rows_lower(gp_ctx *ctx, double *Vt, int mp, const double *L, int np, int ldl, const double *dinv, double *sumsq,
-                          const double *tvec, double *dots) { solve_rows_lower(ctx, Vt, mp, L, np, ldl, dinv, sumsq, tvec, dots); }
+                          const double *tvec, double *dots, const double *Lw) { solve_rows_lower(ctx, Vt, mp, L, np, ldl, dinv, sumsq, tvec, dots, Lw); }
+void gpi_build_lw(gp_ctx *ctx, double *Lw, double *scratch, const double *L, int np, int ldl, const double *dinv) { build_lw(ctx, Lw, scratch, L, np, ldl, dinv); }
+int gpi_rows_left_min() { return rows_left_min(); }
 void gpi_inverse_transpose_lower(gp_ctx *ctx, double *T, const double *L, int np, int ldl, const double *dinv) { inverse_transpose_lower(ctx, T, L, np, ldl, dinv); }
 void gpi_back_solve_vec(gp_ctx *ctx, const double *L, int np, int ldl, const double *dinv, double *z, double *alpha) { back_solve_vec(ctx, L, np, ldl, dinv, z, alpha); }
 gp_status gpi_model_alloc(gp_ctx *ctx, int n, int d, bool has_x, gp_model **out) { return model_alloc(ctx, n, d, has_x, out); }

@@ -55,6 +55,13 @@ struct gp_ep {
     bool sig_mirrored = false;    // the strict upper triangle of Sig mirrors the lower one (only gp_ep_get needs it)
     int *y = nullptr;
     int sweeps = 0;
+    // gp_ep_create_rbf only: the training inputs and the kernel K was built from (gp_ep_predict_rbf rebuilds K* with them)
+    int d = 0;
+    double *dX = nullptr;       // n x d, ld = n
+    double *dcen = nullptr;     // d: centroid of the rows of dX (centre of the matrix-core Gram forms)
+    std::vector<double> theta;  // d + 2
+    double *Lw = nullptr;       // np x np folded factor of large classify batches (gpi_build_lw), allocated on first use
+    bool lw_valid = false;      // Lw belongs to the L now in place: cleared wherever L changes
     double *tau() { return vec; }
     double *nu() { return vec + np; }
     double *tau_old() { return vec + 2 * (size_t)np; }
@@ -826,6 +833,62 @@ __global__ void ep_prob_kernel(double *__restrict__ prob, const double *__restri
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) prob[i] = pnorm_d(fmean[i] / sqrt(1.0 + (kss[i] - sumsq[i])));   // GpClassifier.scala:43-45
 }
+// the same for the kernel's constant test diagonal kss = sf^2 + sn^2; also hands out the latent mean (:37) and variance (diagonal of :41)
+__global__ void ep_prob_latent_kernel(double *__restrict__ prob, double *__restrict__ fmean_out, double *__restrict__ fvar_out,
+                                      const double *__restrict__ fmean, const double *__restrict__ sumsq, double kss, int m) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const double fm = fmean[i], fv = kss - sumsq[i];
+    prob[i] = pnorm_d(fm / sqrt(1.0 + fv));
+    if (fmean_out) fmean_out[i] = fm;
+    if (fvar_out) fvar_out[i] = fv;
+}
+
+// One pass over a batch of the test-train block Vt (mp x np, column-major, ld mp; rows < m and columns < n hold K*) in front of the
+// row solve of GpClassifier.scala:38-41:
+//   fmean[r] = sum_{j<n} K*[r,j] w[j]  (:37),   K*[r,j] <- K*[r,j] st[j]  (:38),   exact zeros in columns n..np-1 and rows m..mp-1
+// (the pad of Vt holds whatever the last user of the workspace left, and nothing guarantees the pad entries of st: both are
+// never read).  A workgroup owns 128 rows: lane l of every wave rows 2l, 2l+1 (16 bytes per lane, a wave reads and writes 1 KiB of a
+// column at a time); wave c owns column chunk c of EP_MS_CHUNKS, so w[j] and st[j] are wave-uniform loads.  The chunk partials meet in
+// LDS and are added in chunk order: no atomics, the same bits on every run.
+constexpr int EP_MS_CHUNKS = 8;
+__global__ __launch_bounds__(64 * EP_MS_CHUNKS) void ep_mean_scale_kernel(double *__restrict__ Vt, int mp, int np, int m, int n,
+                                                                          const double *__restrict__ w, const double *__restrict__ st,
+                                                                          double *__restrict__ fmean) {
+    __shared__ double part[EP_MS_CHUNKS][GP_NB];
+    const int lane = threadIdx.x & 63;
+    const int ch = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int r0 = blockIdx.x * GP_NB + 2 * lane;          // < mp: the grid is mp / 128 workgroups
+    const bool live0 = r0 < m, live1 = r0 + 1 < m;
+    const int cw = np / EP_MS_CHUNKS;                      // np is a multiple of 128
+    const int j0 = ch * cw, j1 = j0 + cw;
+    const int jn = n < j0 ? j0 : (n < j1 ? n : j1);        // [j0, jn): columns of K*, [jn, j1): pad
+    double2 *col = reinterpret_cast<double2 *>(Vt + r0 + (size_t)j0 * mp);     // r0 and mp are even: 16-byte aligned
+    const size_t stride = (size_t)mp / 2;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll 8
+    for (int j = j0; j < jn; ++j, col += stride) {
+        const double wj = w[j], sj = st[j];
+        double2 v = *col;
+        v.x = live0 ? v.x : 0.0;
+        v.y = live1 ? v.y : 0.0;
+        a0 = fma(v.x, wj, a0);
+        a1 = fma(v.y, wj, a1);
+        v.x *= sj;
+        v.y *= sj;
+        *col = v;
+    }
+    for (int j = jn; j < j1; ++j, col += stride) *col = make_double2(0.0, 0.0);
+    part[ch][2 * lane] = a0;
+    part[ch][2 * lane + 1] = a1;
+    __syncthreads();
+    if (threadIdx.x < GP_NB) {
+        double acc = part[0][threadIdx.x];
+#pragma unroll
+        for (int c = 1; c < EP_MS_CHUNKS; ++c) acc += part[c][threadIdx.x];
+        fmean[blockIdx.x * GP_NB + threadIdx.x] = acc;
+    }
+}
 
 // EP log marginal likelihood (EpParameterEstimator.scala:71-96); strict: the fourth/first term is dropped as compiled
 __global__ __launch_bounds__(1024) void ep_lml_kernel(int n, int ldl, const double *__restrict__ L, const double *__restrict__ tau,
@@ -1022,6 +1085,7 @@ gp_status ep_start(gp_ep *ep) {
     ep->sig_mirrored = true;
     ep->side_pending = false;
     ep->sweeps = 0;
+    ep->lw_valid = false;
     GP_HIP(ctx, hipStreamSynchronize(s));
     return GP_OK;
 }
@@ -1108,6 +1172,7 @@ gp_status ep_sweep_lockstep(ep_slab &sl, int count) {
     gp_ctx *ctx = sl.ctx;
     GP_TRY(gpi_ctx_ep_streams(ctx));
     gp_ep *e0 = sl.ep[0];
+    for (int g = 0; g < count; ++g) sl.ep[g]->lw_valid = false;     // every problem's L is rewritten
     // The fourth stream is CU-masked for the single run's sake (64 CUs kept free of its long GEMMs so that the chain's small kernels
     // find a CU); a batch is bound by GEMM throughput instead and loses by the mask (12 problems at n = 4096, aggregate sweeps/s with
     // 0 / 32 / 64 / 96 CUs reserved: 289 / 281 / 271 / 245), so its long GEMMs go to the unmasked third stream behind the factorisation
@@ -1224,6 +1289,7 @@ gp_status gp_ep_sweep(gp_ep *ep, int nsweeps, double *tau, double *nu, int *info
     hipStream_t s = ctx->stream;
     const int n = ep->n, np = ep->np;
     if (info) *info = 0;
+    if (nsweeps > 0) ep->lw_valid = false;     // every sweep ends with a new L (both refactorisation forms)
     GP_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
     // GPCORE_EP_OVERLAP=0: every launch of a site block on one stream (the form the overlapped one is tested against)
     const bool overlap = [] { const char *e = getenv("GPCORE_EP_OVERLAP"); return !e || atoi(e) != 0; }();
@@ -1438,6 +1504,7 @@ gp_status gp_ep_set_site_params(gp_ep *ep, const double *tau, const double *nu, 
     GP_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->stream));
     GP_TRY(gpi_upload_2d(ctx, ep->tau(), ep->np, tau, ep->n, ep->n, 1));
     GP_TRY(gpi_upload_2d(ctx, ep->nu(), ep->np, nu, ep->n, ep->n, 1));
+    ep->lw_valid = false;
     GP_TRY(ep_refactor(ep));
     GP_TRY(ep_join_side(ep));
     int h = 0;
@@ -1563,6 +1630,112 @@ gp_status gp_ep_predict(gp_ep *ep, const double *Ks, int m, int ldks, const doub
     gpi_solve_rows_lower(ctx, Vt, mp, ep->L, np, ep->ldl, ep->dinv, sumsq, nullptr, nullptr);
     hipLaunchKernelGGL(ep_prob_kernel, g1(m), dim3(256), 0, s, dout + mp, dout, sumsq, dk, m);
     return gpi_download_2d(ctx, prob, m, dout + mp, m, m, 1);
+}
+
+// The classifier from data: K = buildKernelMatrix(GaussianRbfKernel(theta), X) on the device (full, pad identity, sn^2 on the
+// diagonal -- as ep_eval_batched builds it per setting); X and theta stay with the object for gp_ep_predict_rbf.
+gp_status gp_ep_create_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *theta, gp_ep **out) {
+    if (!ctx || !out) return GP_EINVAL;
+    *out = nullptr;
+    GP_REQUIRE(ctx, X && y && theta && n >= 1 && d >= 1 && d <= 64 && ldx >= n, "bad arguments (1 <= d <= 64)");
+    gp_ep *ep = nullptr;
+    GP_TRY(ep_alloc(ctx, n, y, &ep));
+    ep->d = d;
+    ep->theta.assign(theta, theta + d + 2);
+    gp_status st = GP_OK;
+    hipError_t e = hipMalloc(&ep->dX, sizeof(double) * (size_t)n * d);
+    if (e == hipSuccess) e = hipMalloc(&ep->dcen, sizeof(double) * 64);
+    if (e != hipSuccess) { (void)hipGetLastError(); GP_SET_ERR(ctx, "EP training inputs (n=%d, d=%d): %s", n, d, hipGetErrorString(e)); st = GP_ENOMEM; }
+    if (st == GP_OK) st = gpi_upload_2d(ctx, ep->dX, n, X, ldx, n, d);
+    if (st == GP_OK) {
+        gpk_centroid(ctx->stream, ep->dX, n, d, n, ep->dcen);
+        gpk_gram_sym(ctx->stream, ep->dX, n, d, n, ep->theta.data(), ep->K, ep->np, 1, 0.0, gp_gram_flag(ctx), ep->dcen);
+        st = ep_start(ep);     // pad identity, Sigma = K; synchronises, so X is no longer read when this returns
+    }
+    if (st == GP_OK && hipGetLastError() != hipSuccess) { GP_SET_ERR(ctx, "EP Gram build (n=%d, d=%d): launch failed", n, d); st = GP_EHIP; }
+    if (st != GP_OK) { gp_ep_destroy(ep); return st; }
+    *out = ep;
+    return GP_OK;
+}
+
+// GpClassifier.classify (GpClassifier.scala:33-45) from test INPUTS in HBM, batch by batch: cross-Gram into Vt, ONE pass for the
+// latent mean, the column scaling and the pad (ep_mean_scale_kernel), Vt <- Vt L^-T with its row sums of squares, probit epilogue.
+gp_status gp_ep_predict_rbf_dev(gp_ep *ep, const double *dXs, int m, int ldxs, int batch_rows, double *dprob, double *dfmean, double *dfvar) {
+    if (!ep) return GP_EINVAL;
+    gp_ctx *ctx = ep->ctx;
+    GP_REQUIRE(ctx, ep->dX, "classifier was built from a Gram matrix");
+    GP_REQUIRE(ctx, dXs && dprob && m >= 0 && ldxs >= m && batch_rows >= 0, "bad arguments");
+    GP_REQUIRE(ctx, ep->sweeps > 0, "classifier not trained: run gp_ep_sweep first");
+    if (m == 0) return GP_OK;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int n = ep->n, np = ep->np, d = ep->d;
+    // rows per batch: the rule of gp_predict_dev (Vt under ~32 GiB, at most 131072 rows) unless the caller names one
+    int batch = batch_rows > 0 ? std::max(GP_NB, batch_rows / GP_NB * GP_NB)
+                               : (int)std::min<size_t>(131072, std::max<size_t>(GP_NB, (((size_t)32 << 30) / ((size_t)np * 8)) / GP_NB * GP_NB));
+    batch = std::min(batch, gp_pad(m));
+    double *Vt, *partial, *sumsq, *fm;
+    GP_TRY(gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)batch * np, &Vt));
+    GP_TRY(gpi_ws_get(ctx, WS_PARTIAL, sizeof(double) * (size_t)16 * np, &partial));
+    GP_TRY(gpi_ws_get(ctx, WS_SUMSQ, sizeof(double) * (size_t)batch, &sumsq));
+    GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)batch, &fm));
+    // large batches: the folded factor of the left-looking solve, kept until L changes
+    const double *Lw = nullptr;
+    if (batch / GP_NB >= gpi_rows_left_min()) {
+        if (!ep->Lw) {
+            hipError_t e = hipMalloc(&ep->Lw, sizeof(double) * (size_t)np * np);
+            if (e != hipSuccess) { (void)hipGetLastError(); ep->Lw = nullptr; GP_SET_ERR(ctx, "hipMalloc(Lw, n=%d) failed: %s", n, hipGetErrorString(e)); return GP_ENOMEM; }
+            ep->lw_valid = false;
+        }
+        if (!ep->lw_valid) {
+            double *scratch;
+            GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)np * np, &scratch));
+            gpi_build_lw(ctx, ep->Lw, scratch, ep->L, np, ep->ldl, ep->dinv);
+            ep->lw_valid = true;
+        }
+        Lw = ep->Lw;
+    }
+    // w = nu - st o L^T \ (L \ (st o (K nu))), once per call                  GpClassifier.scala:33-36
+    double *w = ep->tmp2();
+    gpk_gemv_rows(s, ep->K, n, n, np, ep->nu(), ep->tmp1(), partial, 16);
+    hipLaunchKernelGGL(vec_mul_kernel, g1(n), dim3(256), 0, s, ep->tmp1(), ep->tmp1(), ep->st(), n);
+    gpi_forward_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp1(), ep->tmp2());
+    gpi_back_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp2(), ep->tmp1());
+    hipLaunchKernelGGL(ep_w_kernel, g1(np), dim3(256), 0, s, w, ep->nu(), ep->st(), ep->tmp1(), n, np);
+    const double sf = ep->theta[0], sn = ep->theta[d + 1];
+    const double kss = sf * sf + sn * sn;      // diagonal of buildKernelMatrix(kernel, X*): the noise is on it
+    for (int lo = 0; lo < m; lo += batch) {
+        const int mb = std::min(batch, m - lo), mp = gp_pad(mb);
+        gp_prof_begin(ctx, GP_PROF_GRAM);
+        gpk_gram_cross(s, dXs + lo, mb, ldxs, ep->dX, n, n, d, ep->theta.data(), Vt, mp, gp_gram_flag(ctx), ep->dcen);
+        gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * mb * (double)n + 8.0 * (mb + n) * d);
+        hipLaunchKernelGGL(ep_mean_scale_kernel, dim3(mp / GP_NB), dim3(64 * EP_MS_CHUNKS), 0, s, Vt, mp, np, mb, n, w, ep->st(), fm);
+        GP_HIP(ctx, hipMemsetAsync(sumsq, 0, sizeof(double) * mp, s));
+        gpi_solve_rows_lower(ctx, Vt, mp, ep->L, np, ep->ldl, ep->dinv, sumsq, nullptr, nullptr, Lw);
+        hipLaunchKernelGGL(ep_prob_latent_kernel, g1(mb), dim3(256), 0, s, dprob + lo, dfmean ? dfmean + lo : nullptr,
+                           dfvar ? dfvar + lo : nullptr, fm, sumsq, kss, mb);
+    }
+    GP_LAUNCH_CHECK(ctx);
+    return GP_OK;
+}
+
+gp_status gp_ep_predict_rbf(gp_ep *ep, const double *Xs, int m, int ldxs, double *prob, double *fmean, double *fvar) {
+    if (!ep) return GP_EINVAL;
+    gp_ctx *ctx = ep->ctx;
+    GP_REQUIRE(ctx, ep->dX, "classifier was built from a Gram matrix");
+    GP_REQUIRE(ctx, Xs && prob && m >= 0 && ldxs >= m, "bad arguments");
+    GP_REQUIRE(ctx, ep->sweeps > 0, "classifier not trained: run gp_ep_sweep first");
+    if (m == 0) return GP_OK;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    double *dXs, *dout;
+    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * ep->d, &dXs));
+    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)3 * m, &dout));
+    GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, ep->d));
+    GP_TRY(gp_ep_predict_rbf_dev(ep, dXs, m, m, 0, dout, fmean ? dout + m : nullptr, fvar ? dout + 2 * (size_t)m : nullptr));
+    GP_TRY(gpi_download_2d(ctx, prob, m, dout, m, m, 1));
+    if (fmean) GP_TRY(gpi_download_2d(ctx, fmean, m, dout + m, m, m, 1));
+    if (fvar) GP_TRY(gpi_download_2d(ctx, fvar, m, dout + 2 * (size_t)m, m, m, 1));
+    return GP_OK;
 }
 
 // EP log marginal likelihood at B hyper-parameter settings of the ARD-RBF kernel: what
@@ -1802,7 +1975,8 @@ void gp_ep_destroy(gp_ep *ep) {
     }
     for (hipEvent_t ev : ep->ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {ep->ev_chol, ep->ev_parta, ep->ev_partb, ep->ev_w, ep->ev_pipe}) if (ev) (void)hipEventDestroy(ev);
-    void *ptrs[] = {ep->K, ep->Sig, ep->Sig2, ep->L, ep->dinv, ep->S, ep->Sc, ep->blk, ep->vec, ep->cvec, ep->y, ep->flags, ep->uflags};
+    void *ptrs[] = {ep->K, ep->Sig, ep->Sig2, ep->L, ep->dinv, ep->S, ep->Sc, ep->blk, ep->vec, ep->cvec, ep->y, ep->flags, ep->uflags,
+                    ep->dX, ep->dcen, ep->Lw};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete ep;
 }

@@ -201,7 +201,11 @@ void gpi_chol_panel_step(gp_ctx *ctx, hipStream_t s, double *A, int np, int lda,
                          hipStream_t far = nullptr, hipEvent_t far_done = nullptr,
                          int count = 1, size_t strideA = 0, size_t strideDinv = 0, int *info = nullptr);   // count > 1: a lockstep batch (info + g per problem)
 void gpi_solve_rows_lower(gp_ctx *ctx, double *Vt, int mp, const double *L, int np, int ldl, const double *dinv, double *sumsq,
-                          const double *tvec = nullptr, double *dots = nullptr);
+                          const double *tvec = nullptr, double *dots = nullptr, const double *Lw = nullptr);   // Lw: see gpi_build_lw
+// the folded factor of the left-looking posterior batches (gpcore_api.hip build_lw): Lw and scratch np x np; gpi_solve_rows_lower takes it
+// from gpi_rows_left_min() row tiles on (GPCORE_ROWS_LEFT_MIN, read per call)
+void gpi_build_lw(gp_ctx *ctx, double *Lw, double *scratch, const double *L, int np, int ldl, const double *dinv);
+int gpi_rows_left_min();
 void gpi_back_solve_vec(gp_ctx *ctx, const double *L, int np, int ldl, const double *dinv, double *z, double *alpha);
 void gpi_inverse_transpose_lower(gp_ctx *ctx, double *T, const double *L, int np, int ldl, const double *dinv);
 void gpi_forward_solve_vec(gp_ctx *ctx, const double *L, int np, int ldl, const double *dinv, double *t, double *z);

@@ -206,6 +206,19 @@ gp_status gp_ep_get(gp_ep *ep, int what, double *out, int ld);
 /* GpClassifier.classify, gp/classification/GpClassifier.scala:24-47: Ks is m x n (test-train),
  * kss_diag[m] the diagonal of the test Gram matrix; prob[m] = Phi(mu*_i / sqrt(1 + var*_i)). */
 gp_status gp_ep_predict(gp_ep *ep, const double *Ks, int m, int ldks, const double *kss_diag, double *prob);
+/* The classifier from DATA, as the reference's callers build it (CancerClassificationTest; MarginalLikelihoodEvaluator.scala:37):
+ * K = buildKernelMatrix(GaussianRbfKernel(theta), X) on the device (sn^2 on the diagonal, KernelRequisites.scala:66-72); the object
+ * keeps X (n x d, 1 <= d <= 64) and theta and otherwise behaves exactly like one from gp_ep_create. */
+gp_status gp_ep_create_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *theta, gp_ep **out);
+/* GpClassifier.classify (GpClassifier.scala:33-45) at m test points Xs (m x d) for an object from gp_ep_create_rbf: the test-train
+ * block buildKernelMatrix(kernel, X*, X) is built on the device and never crosses the boundary; the test diagonal is the
+ * constant sf^2 + sn^2 (buildKernelMatrix(kernel, X*) puts the noise there).  prob[m] = :44; fmean[m] = :37 and fvar[m] = the
+ * diagonal of :41 are optional (NULL).  GP_EINVAL for an object from gp_ep_create and before the first sweep. */
+gp_status gp_ep_predict_rbf(gp_ep *ep, const double *Xs, int m, int ldxs, double *prob, double *fmean, double *fvar);
+/* The same with test points and results in HBM, asynchronous on the context's stream, in batches of batch_rows test points
+ * (rounded down to a multiple of 128, at least 128; 0 = the rule of gp_predict_dev: the m x n block under ~32 GiB, at most
+ * 131072 rows), so that m is unbounded. */
+gp_status gp_ep_predict_rbf_dev(gp_ep *ep, const double *dXs, int m, int ldxs, int batch_rows, double *dprob, double *dfmean, double *dfvar);
 /* EP log marginal likelihood over B ARD-RBF hyper-parameter settings (thetas B x (d+2) row-major), by setting index:
  * MeshHyperParamsLogLikelihoodEvaluator.recEvaluate, gp/classification/MeshHyperParamsLogLikelihoodEvaluator.scala:26-40, calling
  * MarginalLikelihoodEvaluator.logLikelihoodWithoutGrad, gp/classification/MarginalLikelihoodEvaluator.scala:24-31, per setting
