@@ -481,6 +481,28 @@ JNIEXPORT jdouble JNICALL Java_gpcore_Native_smallMaximizeUcb(JNIEnv *env, jclas
     free(B); free(S);
     return best;
 }
+/* The same two on the large regression model (gp_fit_rbf; no limit on n): gp_model_ucb / gp_model_maximize_ucb, the objective of
+ * GPOptimizer.maximizeUCB (GPOptimizer.scala:88-106) and its c lockstep L-BFGS runs (:55-63) past GP_SMALL_MAX_N observations */
+JNIEXPORT void JNICALL Java_gpcore_Native_modelUcb(JNIEnv *env, jclass k, jlong h, jlong m, jdoubleArray xs, jint xsoff, jint mm, jint d, jint ldxs,
+                                                   jdouble kappa, jdoubleArray value, jdoubleArray grad) {
+    double *XS = in_d(env, xs, xsoff, span(mm, d, ldxs)), *V = XS ? out_d(env, mm) : NULL, *G = V ? out_d(env, (jsize)mm * d) : NULL;
+    if (G) {
+        gp_status st = gp_model_ucb(MODEL(m), XS, mm, ldxs, kappa, V, G);
+        if (st != GP_OK) throw_for(env, CTX(h), st, 0); else { put_d(env, value, 0, V, mm); put_d(env, grad, 0, G, (jsize)mm * d); }
+    }
+    free(G); free(V); free(XS);
+}
+JNIEXPORT jdouble JNICALL Java_gpcore_Native_modelMaximizeUcb(JNIEnv *env, jclass k, jlong h, jlong m, jdoubleArray starts, jint c, jint d,
+                                                              jdouble kappa, jint maxIter, jint history, jdoubleArray bestX) {
+    double best = 0.0;
+    double *S = in_d(env, starts, 0, (jsize)c * d), *B = S ? out_d(env, d) : NULL;
+    if (B) {
+        gp_status st = gp_model_maximize_ucb(MODEL(m), S, c, c, kappa, maxIter, history, B, &best, NULL);
+        if (st != GP_OK) throw_for(env, CTX(h), st, 0); else put_d(env, bestX, 0, B, d);
+    }
+    free(B); free(S);
+    return best;
+}
 
 /* ---- Co2Kernel (Co2Prediction.scala:29-137) ---- */
 JNIEXPORT jlong JNICALL Java_gpcore_Native_fitCo2(JNIEnv *env, jclass k, jlong h, jdoubleArray x, jint n, jdoubleArray y, jdoubleArray theta,

@@ -20,7 +20,9 @@ import utils.StatsUtils._
   *     through GaussianRbfKernel.gradient, utils/KernelRequisites.scala:95-107, on the device);
   *   - any other GradientBasedOptimizer keeps driving the search itself, one start at a time as in the reference, with the
   *     objective of :88-106 evaluated by ONE launch per trial point (gp_small_ucb) instead of computePosterior + two derivative
-  *     matrices + a product with L^-1 on the host.
+  *     matrices + a product with L^-1 on the host;
+  *   - past GP_SMALL_MAX_N observations the same two paths run on the large regression model (gp_model_maximize_ucb / gp_model_ucb
+  *     over gp_predict_grad), refitted per accepted point.
   * `KernelFunc.gradient` is implemented by GaussianRbfKernel only (Co2Kernel's is `???`, Co2Prediction.scala:62-64), so that is
   * the kernel this class has ever worked with; anything else fails the `require` below instead of the reference's NotImplementedError. */
 class GPOptimizer(@BeanProperty var gpPredictor: GpPredictor, noise: Option[Double], gradientOptimizer: GradientBasedOptimizer) {
@@ -43,51 +45,74 @@ class GPOptimizer(@BeanProperty var gpPredictor: GpPredictor, noise: Option[Doub
     val hp: KernelFuncHyperParams =
       if (params.optimizeHpOnInitGrid) gpPredictor.obtainOptimalHyperParams(pointGrid, noise, evaluatedPointGrid, true) else hyperParams
     val (n0, d) = (pointGrid.rows, pointGrid.cols)
-    require(n0 + m <= SmallMaxN, s"3 d + m = ${n0 + m} exceeds GP_SMALL_MAX_N = $SmallMaxN")
 
-    // the point set and its values grow on the host exactly as in the reference (:47-72); the model grows on the device
+    // the point set and its values grow on the host exactly as in the reference (:47-72); the model grows on the device: up to
+    // GP_SMALL_MAX_N observations as a gp_small with its O(n^2) append, above that as a large model (gp_fit_rbf) refitted per
+    // accepted point, which is what the reference does at every size (:51)
     var points = Vector.tabulate(n0)(i => pointGrid(i, ::).t.toArray)
     var values = evaluatedPointGrid.toArray.toVector
-    val x = dense(pointGrid)
-    val small = rethrowNotPd {
-      Native.smallFit(ctx, x.data, x.offset, n0, d, x.majorStride, evaluatedPointGrid.toArray, 1, hp.toDenseVector.toArray,
-        noise.getOrElse(Double.NaN), n0 + m)
+    val theta = hp.toDenseVector.toArray
+    val sigmaNoise = noise.getOrElse(Double.NaN)
+    val capacity = math.min(n0 + m, SmallMaxN)
+    def fitLarge(pts: Vector[Array[Double]], vals: Vector[Double]): Long = {
+      val x = DenseMatrix.tabulate(pts.length, d)((i, j) => pts(i)(j))
+      rethrowNotPd { Native.fitRbf(ctx, x.data, x.offset, pts.length, d, x.majorStride, vals.toArray, theta, sigmaNoise) }
     }
+    var small = 0L
+    var large = 0L
+    if (n0 <= SmallMaxN) {
+      val x = dense(pointGrid)
+      small = rethrowNotPd { Native.smallFit(ctx, x.data, x.offset, n0, d, x.majorStride, evaluatedPointGrid.toArray, 1, theta, sigmaNoise, capacity) }
+    } else large = fitLarge(points, values)
     try {
       for (iterNum <- 0 until m) {
         val asMatrix = DenseMatrix.tabulate(points.length, d)((i, j) => points(i)(j))
         val (observedMean, observedCov) = meanAndVarOfData(asMatrix)                        // :52
         val sampler = new NormalDistributionSampler(GaussianDistribution(mean = observedMean, sigma = observedCov))
         val starts = Array.fill(c)(sampler.sample.toArray)                                  // :57, one start per L-BFGS run
-        val (biggestUcb, found) = maximizeUcbOnDevice(small, starts, d, k)
+        val (biggestUcb, found) = maximizeUcbOnDevice(small, large, starts, d, k)
         val biggestUcbPoint = if (found.isEmpty || biggestUcb.isNaN) sampler.sample.toArray else found.get   // :64
         try {
           val evaluated = func(biggestUcbPoint)                                             // :66-69
-          rethrowNotPd { Native.smallAppend(ctx, small, d, 1, biggestUcbPoint, Array(evaluated)) }
+          if (small != 0L && points.length < capacity)
+            rethrowNotPd { Native.smallAppend(ctx, small, d, 1, biggestUcbPoint, Array(evaluated)) }
+          else {
+            val refit = fitLarge(points :+ biggestUcbPoint, values :+ evaluated)
+            if (small != 0L) { Native.smallDestroy(small); small = 0L }
+            if (large != 0L) Native.modelDestroy(large)
+            large = refit
+          }
           points = points :+ biggestUcbPoint
           values = values :+ evaluated
         } catch {
           case _: Exception =>                                                              // :70-72: the sets stay as they were
         }
       }
-    } finally Native.smallDestroy(small)
+    } finally {
+      if (small != 0L) Native.smallDestroy(small)
+      if (large != 0L) Native.modelDestroy(large)
+    }
     val maxIndex = values.indices.foldLeft(0)((best, i) => if (values(i) > values(best)) i else best)   // first maximum, :73-78
     (points(maxIndex), values(maxIndex))
   }
 
-  /** The c runs of maximizeUCB (:55-63, 82-109) of one iteration against the resident model: (best UCB, its point). */
-  private def maximizeUcbOnDevice(small: Long, starts: Array[Array[Double]], d: Int, kParam: Double): (Double, Option[Array[Double]]) =
+  /** The c runs of maximizeUCB (:55-63, 82-109) of one iteration against the resident model -- the gp_small while there is one,
+    * else the large model: (best UCB, its point). */
+  private def maximizeUcbOnDevice(small: Long, large: Long, starts: Array[Array[Double]], d: Int, kParam: Double): (Double, Option[Array[Double]]) =
     lbfgsMaxIter(gradientOptimizer) match {
       case Some(maxIter) =>      // the reference's optimiser: all c runs in lockstep on the device (L-BFGS m = 4, Optimization.scala:34-35)
         val c = starts.length
         val colMajor = Array.tabulate(c * d)(idx => starts(idx % c)(idx / c))               // c x d, column-major
         val bestX = new Array[Double](d)
-        val best = Native.smallMaximizeUcb(ctx, small, 0, colMajor, c, d, kParam, maxIter, 4, bestX)
+        val best =
+          if (small != 0L) Native.smallMaximizeUcb(ctx, small, 0, colMajor, c, d, kParam, maxIter, 4, bestX)
+          else Native.modelMaximizeUcb(ctx, large, colMajor, c, d, kParam, maxIter, 4, bestX)
         (best, Some(bestX))
       case None =>               // somebody else's optimiser drives: one launch per trial point
         val objective: objectiveFunctionWithGradient = { testPoint =>
           val value = new Array[Double](1); val grad = new Array[Double](d)
-          Native.smallUcb(ctx, small, 0, testPoint, 0, 1, d, 1, kParam, value, grad)
+          if (small != 0L) Native.smallUcb(ctx, small, 0, testPoint, 0, 1, d, 1, kParam, value, grad)
+          else Native.modelUcb(ctx, large, testPoint, 0, 1, d, 1, kParam, value, grad)
           (value(0), grad)
         }
         starts.foldLeft[(Double, Option[Array[Double]])]((Double.MinValue, None)) { case ((bestVal, bestPoint), start) =>

@@ -52,6 +52,9 @@ object Native {
   @native def smallUcb(ctx: Long, small: Long, g: Int, xs: Array[Double], xsoff: Int, m: Int, d: Int, ldxs: Int, kappa: Double, value: Array[Double], grad: Array[Double]): Unit
   @native def smallAppend(ctx: Long, small: Long, d: Int, g: Int, xNew: Array[Double], yNew: Array[Double]): Unit
   @native def smallMaximizeUcb(ctx: Long, small: Long, g: Int, starts: Array[Double], c: Int, d: Int, kappa: Double, maxIter: Int, history: Int, bestX: Array[Double]): Double
+  // the same objective and optimiser on the large regression model (fitRbf): no limit on n
+  @native def modelUcb(ctx: Long, model: Long, xs: Array[Double], xsoff: Int, m: Int, d: Int, ldxs: Int, kappa: Double, value: Array[Double], grad: Array[Double]): Unit
+  @native def modelMaximizeUcb(ctx: Long, model: Long, starts: Array[Double], c: Int, d: Int, kappa: Double, maxIter: Int, history: Int, bestX: Array[Double]): Double
   // Co2Kernel
   @native def gramCo2(ctx: Long, x: Array[Double], n: Int, theta: Array[Double], out: Array[Double]): Unit
   @native def dgramCo2(ctx: Long, x: Array[Double], n: Int, theta: Array[Double], pos: Int, out: Array[Double]): Unit

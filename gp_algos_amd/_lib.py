@@ -12,7 +12,7 @@ GP_OK, GP_EINVAL, GP_ENOTPD, GP_ENOMEM, GP_EHIP, GP_ERANGE, GP_ERCCL, GP_EPEER =
 GP_DIST_ID_BYTES = 128
 GP_LOWER, GP_FULL = 0, 1
 GP_GET_L, GP_GET_ALPHA, GP_GET_LML = 0, 1, 2
-GP_PROF_OFF, GP_PROF_GEMM, GP_PROF_SYRK, GP_PROF_GRAM, GP_PROF_TRSM, GP_PROF_POTRF_DIAG, GP_PROF_PANEL_UPD = range(7)
+GP_PROF_OFF, GP_PROF_GEMM, GP_PROF_SYRK, GP_PROF_GRAM, GP_PROF_TRSM, GP_PROF_POTRF_DIAG, GP_PROF_PANEL_UPD, GP_PROF_PREDICT_GRAD = range(8)
 GP_EP_GET_L, GP_EP_GET_SIGMA, GP_EP_GET_MU, GP_EP_GET_CAV_TAU, GP_EP_GET_CAV_NU = range(5)
 GP_SMALL_GET_L, GP_SMALL_GET_LINV, GP_SMALL_GET_ALPHA = range(3)
 GP_SMALL_MAX_N = 2048
@@ -57,6 +57,10 @@ SIGNATURES = {
     "gp_model_destroy": (None, [_vp]),
     "gp_predict": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _i]),
     "gp_predict_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "gp_predict_grad_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "gp_predict_grad": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _dp, _i]),
+    "gp_model_ucb": (_i, [_vp, _dp, _i, _i, _d, _dp, _dp]),
+    "gp_model_maximize_ucb": (_i, [_vp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip]),
     "gp_posterior_from_factor": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _dp, _dp, _i, _dp, _i]),
     "gp_posterior_from_gram": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _i, _dp, _i]),
     "gp_predict_from_gram": (_i, [_vp, _dp, _i, _i, _dp, _i, _dp, _dp, _dp, _dp, _i]),

@@ -389,6 +389,57 @@ class RegressionModel:
                                                 L.dptr(cov) if full_cov else None, max(m, 1)))
         return mean, var, cov
 
+    def _test_points(self, Xs):
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if self.d >= 1 and Xs.ndim == 2 and Xs.shape[1] != self.d:
+            raise ValueError("test data dimension mismatch")
+        return L.f64(Xs.reshape(-1, max(self.d, 1)))       # a model without inputs (d = 0) is refused by the library, with its message
+
+    def predict_grad(self, Xs, batch_rows=0):
+        """gp_predict_grad: (mean[m], var[m], gmean[m, d], gvar[m, d]) -- the posterior of predict() and its gradients w.r.t. the
+        test points.  batch_rows != 0 takes the device-pointer entry (gp_predict_grad_dev) with that many test points per batch."""
+        Xs = self._test_points(Xs)
+        batch_rows = int(batch_rows)
+        if batch_rows < 0:
+            raise ValueError("batch_rows < 0")
+        m, d = Xs.shape
+        lib, ctx = self.ctx._lib, self.ctx
+        mean, var = np.zeros(m), np.zeros(m)
+        gmean, gvar = np.zeros((m, d), order="F"), np.zeros((m, d), order="F")
+        if batch_rows == 0 or m == 0:
+            ctx.check(lib.gp_predict_grad(self.h, L.dptr(Xs), m, max(m, 1), L.dptr(mean), L.dptr(var), L.dptr(gmean), L.dptr(gvar), max(m, 1)))
+            return mean, var, gmean, gvar
+        dXs = ctx.upload(Xs)
+        dout = None
+        try:
+            dout = ctx.dev_alloc((2 + 2 * d) * m * 8)
+            dp = lambda k: C.c_void_p(dout.value + k * m * 8)
+            ctx.check(lib.gp_predict_grad_dev(self.h, dXs, m, m, batch_rows, dp(0), dp(1), dp(2), dp(2 + d), m))
+            ctx.sync()
+            out = ctx.download(dout, (m, 2 + 2 * d))
+        finally:
+            ctx.dev_free(dXs)
+            if dout is not None:
+                ctx.dev_free(dout)
+        return (np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]), np.asfortranarray(out[:, 2:2 + d]),
+                np.asfortranarray(out[:, 2 + d:]))
+
+    def ucb(self, Xs, kappa):
+        """gp_model_ucb: (value[m], grad[m, d]) of mean + kappa sqrt(var), the shapes of SmallModelBatch.ucb."""
+        Xs = self._test_points(Xs)
+        m = Xs.shape[0]
+        val, grad = np.zeros(m), np.zeros((m, self.d))
+        self.ctx.check(self.ctx._lib.gp_model_ucb(self.h, L.dptr(Xs), m, max(m, 1), float(kappa), L.dptr(val), L.dptr(grad)))
+        return val, grad
+
+    def maximize_ucb(self, starts, kappa, max_iter=10, history=4):
+        """gp_model_maximize_ucb: (best_x[d], best_value, evaluations) over c lockstep L-BFGS runs, as SmallModelBatch.maximize_ucb."""
+        starts = self._test_points(starts)
+        c = starts.shape[0]
+        bx, bv, ev = np.zeros(self.d), C.c_double(), C.c_int()
+        self.ctx.check(self.ctx._lib.gp_model_maximize_ucb(self.h, L.dptr(starts), c, max(c, 1), float(kappa), int(max_iter), int(history),
+                                                           L.dptr(bx), C.byref(bv), C.byref(ev)))
+        return bx, bv.value, ev.value
 
     def predict_from_gram(self, Ks, Kss=None, kss_diag=None):
         """gp_predict_from_gram: posterior for a model fitted from a host-built Gram matrix; (mean, var|None, cov|None)."""

@@ -653,7 +653,9 @@ void solve_rows_upper(gp_ctx *ctx, double *Vt, int mp, const double *U, int np, 
                         U + (size_t)i * GP_NB + (size_t)(i + 1) * GP_NB * ldu, ldu, 1.0, Vi, mp, 0);
             gp_prof_end(ctx, GP_PROF_GEMM, 2.0 * mp * GP_NB * (double)kr);
         }
+        gp_prof_begin(ctx, GP_PROF_TRSM);
         gpk_trsm_panel_upper(s, Vi, mp, mp, U + (size_t)i * GP_NB + (size_t)i * GP_NB * ldu, ldu);
+        gp_prof_end(ctx, GP_PROF_TRSM, (double)mp * GP_NB * GP_NB);
     }
 }
 
@@ -694,6 +696,8 @@ void model_factor(gp_model *m) {
     gpk_copy_strided(s, m->dtmp, 1, m->dL + m->np, (size_t)m->ldl, m->np);     // t = L^-1 y
     m->alpha_valid = false;
     m->lw_valid = false;
+    m->lt_valid = false;
+    m->info_known = false;
     gpk_lml(s, m->dL, m->n, m->ldl, m->dtmp, m->dlml);
 }
 
@@ -1211,6 +1215,7 @@ gp_status gp_model_status(gp_model *m, int *info) {
     int h = 0;
     GP_TRY(read_info(m->ctx, &h));
     m->last_info = h;
+    m->info_known = true;
     if (info) *info = h;
     if (h) { GP_SET_ERR(m->ctx, "matrix not positive definite at pivot %d", h); return GP_ENOTPD; }
     return GP_OK;
@@ -1353,6 +1358,7 @@ void gp_model_destroy(gp_model *m) {
     if (m->dtmp) (void)hipFree(m->dtmp);
     if (m->dlml) (void)hipFree(m->dlml);
     if (m->dLw) (void)hipFree(m->dLw);
+    if (m->dLt) (void)hipFree(m->dLt);
     delete m;
 }
 
@@ -1405,6 +1411,12 @@ static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs,
     return GP_OK;
 }
 
+// most rows of one posterior batch: GPCORE_PREDICT_BATCH (a multiple of 128, read once), else 131072
+static int predict_batch_cap() {
+    static const int cap = [] { const char *e = getenv("GPCORE_PREDICT_BATCH"); int v = e ? atoi(e) : 0; return v >= GP_NB ? v / GP_NB * GP_NB : 131072; }();
+    return cap;
+}
+
 gp_status gp_predict_dev(gp_model *mdl, const double *dXs, int m, int ldxs, double *dmean, double *dvar) {
     if (!mdl) return GP_EINVAL;
     gp_ctx *ctx = mdl->ctx;
@@ -1416,8 +1428,7 @@ gp_status gp_predict_dev(gp_model *mdl, const double *dXs, int m, int ldxs, doub
     // of 512 resident tiles), 131 072 (two rounds) measured +0.9 % at n = 8192, more rows nothing (GPCORE_PREDICT_BATCH).
     const size_t budget = (size_t)32 << 30;
     int batch = (int)std::min<size_t>((size_t)m, std::max<size_t>(GP_NB, (budget / ((size_t)mdl->np * 8)) / GP_NB * GP_NB));
-    static const int batch_cap = [] { const char *e = getenv("GPCORE_PREDICT_BATCH"); int v = e ? atoi(e) : 0; return v >= GP_NB ? v / GP_NB * GP_NB : 131072; }();
-    batch = std::min(batch, batch_cap);
+    batch = std::min(batch, predict_batch_cap());
     for (int lo = 0; lo < m; lo += batch) {
         const int mb = std::min(batch, m - lo);
         GP_TRY(predict_core(mdl, dXs + lo, mb, ldxs, dmean + lo, dvar ? dvar + lo : nullptr, nullptr, nullptr));
@@ -1458,6 +1469,126 @@ gp_status gp_predict(gp_model *mdl, const double *Xs, int m, int ldxs, double *m
             for (int i = 0; i < j; ++i) cov[i + (size_t)j * ldc] = cov[j + (size_t)i * ldc];
     }
     return GP_OK;
+}
+
+// ---- posterior with input gradients (GP-UCB on the large model) ---------------------------------
+// Per batch: predict_core leaves V = K* L^-T in the workspace (mean and variance are ITS results), one more row solve against the cached
+// upper factor L^T turns it IN PLACE into W = V L^-1 = K* K^-1, and gpk_predict_grad streams W once.  k*_ij is recomputed in that pass,
+// so the batch still owns ONE m x n workspace and the row rule is gp_predict_dev's.
+static gp_status predict_grad_checks(gp_model *mdl, const void *xs, const void *mean, int m, int ldxs, bool grads, int ldg) {
+    gp_ctx *ctx = mdl->ctx;
+    GP_REQUIRE(ctx, mdl->has_x && mdl->kind == 0, "input gradients need an ARD-RBF model fitted from training inputs (gp_fit_rbf), not one from a Gram matrix or gp_fit_co2");
+    GP_REQUIRE(ctx, m >= 0, "m < 0");
+    if (m == 0) return GP_OK;
+    GP_REQUIRE(ctx, xs && mean, "null pointer");
+    GP_REQUIRE(ctx, ldxs >= m, "ldxs < m");
+    GP_REQUIRE(ctx, !grads || ldg >= m, "ldg < m");
+    return GP_OK;
+}
+
+gp_status gp_predict_grad_dev(gp_model *mdl, const double *dXs, int m, int ldxs, int batch_rows, double *dmean, double *dvar, double *dgmean,
+                              double *dgvar, int ldg) {
+    if (!mdl) return GP_EINVAL;
+    gp_ctx *ctx = mdl->ctx;
+    GP_TRY(predict_grad_checks(mdl, dXs, dmean, m, ldxs, dgmean || dgvar, ldg));
+    GP_REQUIRE(ctx, batch_rows >= 0, "batch_rows < 0");
+    if (m == 0) return GP_OK;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!mdl->info_known) GP_TRY(gp_model_status(mdl, nullptr));    // a refit since the last look at the factor's status: one synchronisation
+    if (mdl->last_info) { GP_SET_ERR(ctx, "matrix not positive definite at pivot %d", mdl->last_info); return GP_ENOTPD; }
+    hipStream_t s = ctx->stream;
+    const int n = mdl->n, np = mdl->np, d = mdl->d;
+    if (dgmean) ensure_alpha(mdl);
+    if (dgvar && !mdl->lt_valid) {
+        if (!mdl->dLt) {
+            hipError_t e = hipMalloc(&mdl->dLt, sizeof(double) * (size_t)np * np);
+            if (e != hipSuccess) { mdl->dLt = nullptr; GP_SET_ERR(ctx, "hipMalloc(L^T, n=%d) failed: %s", n, hipGetErrorString(e)); return GP_ENOMEM; }
+        }
+        gpk_transpose(s, mdl->dLt, np, mdl->dL, mdl->ldl, np, np);
+        mdl->lt_valid = true;
+    }
+    // rows per batch: the rule of gp_predict_dev (the one m x n workspace under ~32 GiB, at most 131072 rows or GPCORE_PREDICT_BATCH)
+    // unless the caller names one
+    const size_t budget = (size_t)32 << 30;
+    int batch = (int)std::min<size_t>((size_t)predict_batch_cap(), std::max<size_t>(GP_NB, (budget / ((size_t)np * 8)) / GP_NB * GP_NB));
+    if (batch_rows > 0) batch = std::max(GP_NB, batch_rows / GP_NB * GP_NB);
+    batch = std::min(batch, gp_pad(m));
+    // The gradient pass's scratch is NOT monotone in the row count (fewer row groups split the training points further: 65472 rows
+    // need about twice what 65536 do), so it is sized for the two batch shapes that run: the full batch and the shorter last one.
+    double *partials = nullptr;
+    size_t need = 0;
+    if (dgmean || dgvar) {
+        const int full = std::min(batch, m), tail = m % batch;
+        need = std::max(gpk_predict_grad_partials(full, n, d), tail ? gpk_predict_grad_partials(tail, n, d) : (size_t)0);
+        GP_TRY(ws_get(ctx, WS_E, sizeof(double) * need, &partials));
+    }
+    for (int lo = 0; lo < m; lo += batch) {
+        const int mb = std::min(batch, m - lo);
+        double *Vt = nullptr;
+        int mp = 0;
+        GP_TRY(predict_core(mdl, dXs + lo, mb, ldxs, dmean + lo, dvar ? dvar + lo : nullptr, &Vt, &mp));
+        if (!dgmean && !dgvar) continue;
+        GP_REQUIRE(ctx, gpk_predict_grad_partials(mb, n, d) <= need, "internal: gradient scratch smaller than this batch needs");
+        if (dgvar) solve_rows_upper(ctx, Vt, mp, mdl->dLt, np, np);
+        gp_prof_begin(ctx, GP_PROF_PREDICT_GRAD);
+        gpk_predict_grad(s, dgvar ? Vt : nullptr, mp, dXs + lo, mb, ldxs, mdl->dX, n, n, d, mdl->theta.data(), mdl->dalpha, partials,
+                         dgmean ? dgmean + lo : nullptr, dgvar ? dgvar + lo : nullptr, ldg);
+        // bytes it must read: W once (when gvar is asked for), the test points, and X and alpha once per 64 test points
+        gp_prof_end(ctx, GP_PROF_PREDICT_GRAD, 8.0 * ((dgvar ? (double)mb * n : 0.0) + (double)mb * d + (double)((mb + 63) / 64) * n * (d + 1.0)));
+        GP_LAUNCH_CHECK(ctx);
+    }
+    return GP_OK;
+}
+
+gp_status gp_predict_grad(gp_model *mdl, const double *Xs, int m, int ldxs, double *mean, double *var, double *gmean, double *gvar, int ldg) {
+    if (!mdl) return GP_EINVAL;
+    gp_ctx *ctx = mdl->ctx;
+    GP_TRY(predict_grad_checks(mdl, Xs, mean, m, ldxs, gmean || gvar, ldg));
+    if (m == 0) return GP_OK;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    const int d = mdl->d;
+    double *dXs, *dout;
+    GP_TRY(ws_get(ctx, WS_A, sizeof(double) * (size_t)m * d, &dXs));
+    GP_TRY(ws_get(ctx, WS_C, sizeof(double) * (size_t)m * (2 + 2 * (size_t)d), &dout));
+    GP_TRY(upload_2d(ctx, dXs, m, Xs, ldxs, m, d));
+    double *dmean = dout, *dvar = dout + m, *dgm = dvar + m, *dgv = dgm + (size_t)m * d;
+    GP_TRY(gp_predict_grad_dev(mdl, dXs, m, m, 0, dmean, var ? dvar : nullptr, gmean ? dgm : nullptr, gvar ? dgv : nullptr, m));
+    GP_TRY(download_2d(ctx, mean, m, dmean, m, m, 1));
+    if (var) GP_TRY(download_2d(ctx, var, m, dvar, m, m, 1));
+    if (gmean) GP_TRY(download_2d(ctx, gmean, ldg, dgm, m, m, d));
+    if (gvar) GP_TRY(download_2d(ctx, gvar, ldg, dgv, m, m, d));
+    return GP_OK;
+}
+
+// GPOptimizer.maximizeUCB's objective (gp/optimization/GPOptimizer.scala:88-106) on the large model: the device delivers mean, variance
+// and their input gradients; value and gradient of mean + kappa sqrt(var) are formed from them here (O(m d))
+gp_status gp_model_ucb(gp_model *mdl, const double *Xs, int m, int ldxs, double kappa, double *value, double *grad) {
+    if (!mdl) return GP_EINVAL;
+    gp_ctx *ctx = mdl->ctx;
+    GP_TRY(predict_grad_checks(mdl, Xs, value, m, ldxs, false, 0));
+    if (m == 0) return GP_OK;
+    GP_REQUIRE(ctx, grad, "null pointer");
+    const int d = mdl->d;
+    std::vector<double> buf((size_t)m * (1 + 2 * (size_t)d));
+    double *var = buf.data(), *gm = var + m, *gv = gm + (size_t)m * d;
+    GP_TRY(gp_predict_grad(mdl, Xs, m, ldxs, value, var, gm, gv, m));
+    for (int i = 0; i < m; ++i) {
+        const double sd = std::sqrt(var[i]), coeff = kappa / (2.0 * sd);
+        value[i] += kappa * sd;
+        for (int k = 0; k < d; ++k) grad[(size_t)i * d + k] = gm[i + (size_t)k * m] + coeff * gv[i + (size_t)k * m];
+    }
+    return GP_OK;
+}
+
+gp_status gp_model_maximize_ucb(gp_model *mdl, const double *starts, int c, int lds, double kappa, int max_iter, int history, double *best_x,
+                                double *best_val, int *evals_out) {
+    if (!mdl) return GP_EINVAL;
+    gp_ctx *ctx = mdl->ctx;
+    GP_REQUIRE(ctx, mdl->has_x && mdl->kind == 0, "input gradients need an ARD-RBF model fitted from training inputs (gp_fit_rbf), not one from a Gram matrix or gp_fit_co2");
+    GP_REQUIRE(ctx, starts && best_x && c >= 1 && lds >= c && max_iter >= 0 && history >= 1, "bad arguments");
+    return gpi_ucb_lbfgs_lockstep(mdl->d, starts, c, lds, max_iter, history,
+                                  [&](const double *pts, int count, double *val, double *grd) { return gp_model_ucb(mdl, pts, count, count, kappa, val, grd); },
+                                  best_x, best_val, evals_out);
 }
 
 }  // extern "C"

@@ -66,6 +66,9 @@ struct gp_model {
     double *dlml = nullptr;          // 1 double on device
     double *dLw = nullptr;           // np x np, lower: block row i = L_ii^-1 [ -L_i,<i | I ], built on demand for large posterior batches
     bool lw_valid = false;
+    double *dLt = nullptr;           // np x np, upper: L^T, built on demand for the input gradients (W = V L^-1 runs against an upper factor)
+    bool lt_valid = false;           // like lw_valid: every (re)fit clears it
+    bool info_known = true;          // last_info is the status of the factor in dL (false between a refit and the next gp_model_status)
     std::vector<double> theta;       // d + 2
     double sigma_noise = NAN;
     int last_info = 0;
@@ -155,6 +158,12 @@ void gpk_gemv_rows(hipStream_t s, const double *Ks, int m, int n, int ldks, cons
 void gpk_lml(hipStream_t s, const double *L, int n, int ldl, const double *t, double *out);
 // var[i] = kss - sumsq[i]
 void gpk_var_finish(hipStream_t s, double *var, const double *sumsq, int m, double kss);
+// input gradients of the posterior mean and variance (kernels_pgrad.hip): Wt = K* K^-1 in row form (m rows, leading dimension ldw, whole
+// 64-row groups readable) or nullptr (no gvar); gmean / gvar m x d column-major with leading dimension ldg, either may be nullptr;
+// partials: gpk_predict_grad_partials(m, n, d) doubles of scratch
+size_t gpk_predict_grad_partials(int m, int n, int d);
+void gpk_predict_grad(hipStream_t s, const double *Wt, int ldw, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d,
+                      const double *theta, const double *alpha, double *partials, double *gmean, double *gvar, int ldg);
 void gpk_copy_2d(hipStream_t s, double *dst, int ldd, const double *src, int lds, int rows, int cols);
 double gpk_probe_mfma(hipStream_t s, int num_cu, int waves_per_simd, double *clock_mhz, double *cycles_per_mfma);
 int gpk_init_diag_kernels();
@@ -193,6 +202,12 @@ gp_status gpi_model_alloc(gp_ctx *ctx, int n, int d, bool has_x, gp_model **out)
 gp_status gpi_lbfgs_maximize(gp_ctx *ctx, int P, int nparams, const double *theta0, int max_iter, int history, int NC,
                              const std::function<gp_status(const double *, int, double *, double *, int *)> &evaluate,
                              double *theta_out, double *f_out, int *iters_out, int *evals_out);
+// The c L-BFGS runs of one GP-UCB iteration (GPOptimizer.scala:55-63) in lockstep, NC = 4 trial steps per run and iteration, best point
+// any evaluation saw: the driver behind gp_small_maximize_ucb and gp_model_maximize_ucb.  evaluate(pts, count, value, grad): UCB value[count]
+// and gradient grad[i * d + k] at `count` points given as the rows of a count x d column-major matrix.
+gp_status gpi_ucb_lbfgs_lockstep(int d, const double *starts, int c, int lds, int max_iter, int history,
+                                 const std::function<gp_status(const double *, int, double *, double *)> &evaluate,
+                                 double *best_x, double *best_val, int *evals_out);
 gp_status gpi_ctx_ep_streams(gp_ctx *ctx);   // side2 / side3, created on first use
 void gpi_chol_blocked(gp_ctx *ctx, double *A, int np, int lda, double *dinv, int extra);
 // one 128-column step (diagonal block k0) of the same two-level factorisation on stream s, for callers that feed the columns

@@ -241,6 +241,106 @@ void small_invert(gp_small *s) {
 
 }  // namespace
 
+// GPOptimizer.maximizeUCB (gp/optimization/GPOptimizer.scala:82-109) for `c` starting points at once: the reference runs
+// gradientOptimizer.maximize (BreezeLbfgsOptimizer, m = 4: optimization/Optimization.scala:30-63) once per start, every
+// objective evaluation one computePosterior with a single test point; here the c L-BFGS runs advance in LOCKSTEP and every
+// iteration evaluates all their trial steps (c x NC points) in ONE launch.  Returns the best point any evaluation saw
+// (the rule of Optimization.scala:44-46,52-55 applied across all starts) and its UCB value.
+gp_status gpi_ucb_lbfgs_lockstep(int d, const double *starts, int c, int lds, int max_iter, int history,
+                                 const std::function<gp_status(const double *, int, double *, double *)> &evaluate,
+                                 double *best_x, double *best_val, int *evals_out) {
+    constexpr int NC = 4;   // trial steps per run and iteration: 1, 1/2, 1/4, 1/8 of the quasi-Newton step
+    struct run_t {
+        std::vector<double> x, gr, dir;
+        double f = 0.0, slope = 0.0;
+        std::vector<std::vector<double>> S, Y;
+        std::vector<double> rho;
+        bool done = false;
+    };
+    std::vector<run_t> runs(c);
+    std::vector<double> pts((size_t)c * NC * d), val((size_t)c * NC), grd((size_t)c * NC * d);
+    int evals = 0;
+    double bf = -INFINITY;
+    std::vector<double> bx(d, 0.0);
+    auto eval = [&](int count) -> gp_status {   // pts: count points as rows of a (count x d) column-major matrix
+        GP_TRY(evaluate(pts.data(), count, val.data(), grd.data()));
+        evals += count;
+        return GP_OK;
+    };
+    auto note = [&](double v, const double *x) { if (std::isfinite(v) && v > bf) { bf = v; std::copy(x, x + d, bx.begin()); } };
+    for (int r = 0; r < c; ++r)
+        for (int k = 0; k < d; ++k) pts[r + (size_t)k * c] = starts[r + (size_t)k * lds];
+    GP_TRY(eval(c));
+    for (int r = 0; r < c; ++r) {
+        run_t &R = runs[r];
+        R.x.resize(d), R.gr.resize(d), R.dir.resize(d);
+        for (int k = 0; k < d; ++k) { R.x[k] = starts[r + (size_t)k * lds]; R.gr[k] = -grd[(size_t)r * d + k]; }   // minimise f = -UCB
+        R.f = -val[r];
+        if (!std::isfinite(R.f)) R.done = true; else note(val[r], R.x.data());
+    }
+    auto dot = [&](const std::vector<double> &a, const std::vector<double> &b) { double t = 0.0; for (int k = 0; k < d; ++k) t += a[k] * b[k]; return t; };
+    for (int it = 0; it < max_iter; ++it) {
+        int active = 0;
+        for (int r = 0; r < c; ++r) {
+            run_t &R = runs[r];
+            if (R.done) continue;
+            const double gn = std::sqrt(dot(R.gr, R.gr));
+            if (gn <= 1e-10 * std::max(1.0, std::fabs(R.f))) { R.done = true; continue; }
+            std::vector<double> q = R.gr, al(R.S.size());
+            for (int h = (int)R.S.size() - 1; h >= 0; --h) { al[h] = R.rho[h] * dot(R.S[h], q); for (int k = 0; k < d; ++k) q[k] -= al[h] * R.Y[h][k]; }
+            const double sc = R.S.empty() ? 1.0 / gn : dot(R.S.back(), R.Y.back()) / dot(R.Y.back(), R.Y.back());
+            for (int k = 0; k < d; ++k) q[k] *= sc;
+            for (size_t h = 0; h < R.S.size(); ++h) { const double be = R.rho[h] * dot(R.Y[h], q); for (int k = 0; k < d; ++k) q[k] += R.S[h][k] * (al[h] - be); }
+            for (int k = 0; k < d; ++k) R.dir[k] = -q[k];
+            R.slope = dot(R.gr, R.dir);
+            if (!(R.slope < 0.0)) { R.S.clear(), R.Y.clear(), R.rho.clear(); for (int k = 0; k < d; ++k) R.dir[k] = -R.gr[k] / gn; R.slope = -gn; }
+            ++active;
+        }
+        if (!active) break;
+        // trial points of every active run: row index = slot * NC + t
+        std::vector<int> slot_of;
+        for (int r = 0; r < c; ++r) if (!runs[r].done) slot_of.push_back(r);
+        const int count = (int)slot_of.size() * NC;
+        for (size_t sidx = 0; sidx < slot_of.size(); ++sidx)
+            for (int t = 0; t < NC; ++t)
+                for (int k = 0; k < d; ++k)
+                    pts[(sidx * NC + t) + (size_t)k * count] = runs[slot_of[sidx]].x[k] + std::ldexp(1.0, -t) * runs[slot_of[sidx]].dir[k];
+        GP_TRY(eval(count));
+        for (size_t sidx = 0; sidx < slot_of.size(); ++sidx) {
+            run_t &R = runs[slot_of[sidx]];
+            int chosen = -1;
+            for (int t = 0; t < NC; ++t) {
+                const size_t e = sidx * NC + t;
+                std::vector<double> xt(d);
+                for (int k = 0; k < d; ++k) xt[k] = pts[e + (size_t)k * count];
+                note(val[e], xt.data());
+                if (chosen < 0 && std::isfinite(val[e]) && -val[e] <= R.f + 1e-4 * std::ldexp(1.0, -t) * R.slope) chosen = t;
+            }
+            if (chosen < 0) { R.done = true; continue; }
+            const size_t e = sidx * NC + chosen;
+            std::vector<double> sv(d), yv(d);
+            for (int k = 0; k < d; ++k) {
+                sv[k] = std::ldexp(1.0, -chosen) * R.dir[k];
+                yv[k] = -grd[e * d + k] - R.gr[k];
+                R.x[k] += sv[k];
+                R.gr[k] = -grd[e * d + k];
+            }
+            const double fnew = -val[e], sy = dot(sv, yv);
+            if (sy > 1e-12 * std::sqrt(dot(sv, sv) * dot(yv, yv))) {
+                if ((int)R.S.size() == history) { R.S.erase(R.S.begin()); R.Y.erase(R.Y.begin()); R.rho.erase(R.rho.begin()); }
+                R.S.push_back(sv), R.Y.push_back(yv), R.rho.push_back(1.0 / sy);
+            }
+            if (std::fabs(R.f - fnew) <= 1e-12 * std::max(1.0, std::fabs(R.f))) R.done = true;
+            R.f = fnew;
+        }
+    }
+    std::copy(bx.begin(), bx.end(), best_x);
+    if (best_val) *best_val = bf;
+    if (evals_out) *evals_out = evals;
+    return GP_OK;
+}
+
+
 extern "C" {
 
 gp_status gp_small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl,
@@ -404,106 +504,14 @@ gp_status gp_small_append(gp_small *s, const double *x_new, const double *y_new,
     return GP_OK;
 }
 
-// GPOptimizer.maximizeUCB (gp/optimization/GPOptimizer.scala:82-109) for `c` starting points at once: the reference runs
-// gradientOptimizer.maximize (BreezeLbfgsOptimizer, m = 4: optimization/Optimization.scala:30-63) once per start, every
-// objective evaluation one computePosterior with a single test point; here the c L-BFGS runs advance in LOCKSTEP and every
-// iteration evaluates all their trial steps (c x NC points) in ONE launch.  Returns the best point any evaluation saw
-// (the rule of Optimization.scala:44-46,52-55 applied across all starts) and its UCB value.
 gp_status gp_small_maximize_ucb(gp_small *s, int g, const double *starts, int c, int lds, double kappa, int max_iter, int history,
                                 double *best_x, double *best_val, int *evals_out) {
     if (!s) return GP_EINVAL;
     gp_ctx *ctx = s->ctx;
     GP_REQUIRE(ctx, starts && best_x && c >= 1 && lds >= c && g >= 0 && g < s->G && max_iter >= 0 && history >= 1, "bad arguments");
-    const int d = s->d;
-    constexpr int NC = 4;   // trial steps per run and iteration: 1, 1/2, 1/4, 1/8 of the quasi-Newton step
-    struct run_t {
-        std::vector<double> x, gr, dir;
-        double f = 0.0, slope = 0.0;
-        std::vector<std::vector<double>> S, Y;
-        std::vector<double> rho;
-        bool done = false;
-    };
-    std::vector<run_t> runs(c);
-    std::vector<double> pts((size_t)c * NC * d), val((size_t)c * NC), grd((size_t)c * NC * d);
-    int evals = 0;
-    double bf = -INFINITY;
-    std::vector<double> bx(d, 0.0);
-    auto eval = [&](int count) -> gp_status {   // pts: count points as rows of a (count x d) column-major matrix
-        GP_TRY(gp_small_ucb(s, g, pts.data(), count, count, kappa, val.data(), grd.data()));
-        evals += count;
-        return GP_OK;
-    };
-    auto note = [&](double v, const double *x) { if (std::isfinite(v) && v > bf) { bf = v; std::copy(x, x + d, bx.begin()); } };
-    for (int r = 0; r < c; ++r)
-        for (int k = 0; k < d; ++k) pts[r + (size_t)k * c] = starts[r + (size_t)k * lds];
-    GP_TRY(eval(c));
-    for (int r = 0; r < c; ++r) {
-        run_t &R = runs[r];
-        R.x.resize(d), R.gr.resize(d), R.dir.resize(d);
-        for (int k = 0; k < d; ++k) { R.x[k] = starts[r + (size_t)k * lds]; R.gr[k] = -grd[(size_t)r * d + k]; }   // minimise f = -UCB
-        R.f = -val[r];
-        if (!std::isfinite(R.f)) R.done = true; else note(val[r], R.x.data());
-    }
-    auto dot = [&](const std::vector<double> &a, const std::vector<double> &b) { double t = 0.0; for (int k = 0; k < d; ++k) t += a[k] * b[k]; return t; };
-    for (int it = 0; it < max_iter; ++it) {
-        int active = 0;
-        for (int r = 0; r < c; ++r) {
-            run_t &R = runs[r];
-            if (R.done) continue;
-            const double gn = std::sqrt(dot(R.gr, R.gr));
-            if (gn <= 1e-10 * std::max(1.0, std::fabs(R.f))) { R.done = true; continue; }
-            std::vector<double> q = R.gr, al(R.S.size());
-            for (int h = (int)R.S.size() - 1; h >= 0; --h) { al[h] = R.rho[h] * dot(R.S[h], q); for (int k = 0; k < d; ++k) q[k] -= al[h] * R.Y[h][k]; }
-            const double sc = R.S.empty() ? 1.0 / gn : dot(R.S.back(), R.Y.back()) / dot(R.Y.back(), R.Y.back());
-            for (int k = 0; k < d; ++k) q[k] *= sc;
-            for (size_t h = 0; h < R.S.size(); ++h) { const double be = R.rho[h] * dot(R.Y[h], q); for (int k = 0; k < d; ++k) q[k] += R.S[h][k] * (al[h] - be); }
-            for (int k = 0; k < d; ++k) R.dir[k] = -q[k];
-            R.slope = dot(R.gr, R.dir);
-            if (!(R.slope < 0.0)) { R.S.clear(), R.Y.clear(), R.rho.clear(); for (int k = 0; k < d; ++k) R.dir[k] = -R.gr[k] / gn; R.slope = -gn; }
-            ++active;
-        }
-        if (!active) break;
-        // trial points of every active run: row index = slot * NC + t
-        std::vector<int> slot_of;
-        for (int r = 0; r < c; ++r) if (!runs[r].done) slot_of.push_back(r);
-        const int count = (int)slot_of.size() * NC;
-        for (size_t sidx = 0; sidx < slot_of.size(); ++sidx)
-            for (int t = 0; t < NC; ++t)
-                for (int k = 0; k < d; ++k)
-                    pts[(sidx * NC + t) + (size_t)k * count] = runs[slot_of[sidx]].x[k] + std::ldexp(1.0, -t) * runs[slot_of[sidx]].dir[k];
-        GP_TRY(eval(count));
-        for (size_t sidx = 0; sidx < slot_of.size(); ++sidx) {
-            run_t &R = runs[slot_of[sidx]];
-            int chosen = -1;
-            for (int t = 0; t < NC; ++t) {
-                const size_t e = sidx * NC + t;
-                std::vector<double> xt(d);
-                for (int k = 0; k < d; ++k) xt[k] = pts[e + (size_t)k * count];
-                note(val[e], xt.data());
-                if (chosen < 0 && std::isfinite(val[e]) && -val[e] <= R.f + 1e-4 * std::ldexp(1.0, -t) * R.slope) chosen = t;
-            }
-            if (chosen < 0) { R.done = true; continue; }
-            const size_t e = sidx * NC + chosen;
-            std::vector<double> sv(d), yv(d);
-            for (int k = 0; k < d; ++k) {
-                sv[k] = std::ldexp(1.0, -chosen) * R.dir[k];
-                yv[k] = -grd[e * d + k] - R.gr[k];
-                R.x[k] += sv[k];
-                R.gr[k] = -grd[e * d + k];
-            }
-            const double fnew = -val[e], sy = dot(sv, yv);
-            if (sy > 1e-12 * std::sqrt(dot(sv, sv) * dot(yv, yv))) {
-                if ((int)R.S.size() == history) { R.S.erase(R.S.begin()); R.Y.erase(R.Y.begin()); R.rho.erase(R.rho.begin()); }
-                R.S.push_back(sv), R.Y.push_back(yv), R.rho.push_back(1.0 / sy);
-            }
-            if (std::fabs(R.f - fnew) <= 1e-12 * std::max(1.0, std::fabs(R.f))) R.done = true;
-            R.f = fnew;
-        }
-    }
-    std::copy(bx.begin(), bx.end(), best_x);
-    if (best_val) *best_val = bf;
-    if (evals_out) *evals_out = evals;
-    return GP_OK;
+    return gpi_ucb_lbfgs_lockstep(s->d, starts, c, lds, max_iter, history,
+                                  [&](const double *pts, int count, double *val, double *grd) { return gp_small_ucb(s, g, pts, count, count, kappa, val, grd); },
+                                  best_x, best_val, evals_out);
 }
 
 }  // extern "C"

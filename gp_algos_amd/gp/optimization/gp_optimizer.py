@@ -8,14 +8,17 @@ class GPOptimizer(gpPredictor, noise, gradientOptimizer) keeps the reference's c
     (gp_small_maximize_ucb); the objective mean + k sqrt(var) and its gradient through GaussianRbfKernel.gradient are evaluated
     on the device.
 The random draws (initial grid, L-BFGS starting points) come from numpy instead of scala.util.Random(System.nanoTime()) /
-commons-math: the reference's trajectory is not reproducible by construction."""
+commons-math: the reference's trajectory is not reproducible by construction.
+Past GP_SMALL_MAX_N observations the loop continues on the large regression model (RegressionModel.maximize_ucb over
+gp_predict_grad), refitted per accepted point as the reference does."""
 from dataclasses import dataclass
 from typing import Sequence
 
 import numpy as np
 
 from ... import default_context
-from ...core import SmallModelBatch
+from ..._lib import GP_SMALL_MAX_N
+from ...core import RegressionModel, SmallModelBatch
 from ...utils.kernel_requisites import GaussianRbfKernel
 from ...utils.stats_utils import meanAndVarOfData
 
@@ -53,28 +56,40 @@ class GPOptimizer:
         if params.optimizeHpOnInitGrid:
             hp = self.gpPredictor.obtainOptimalHyperParams(pointGrid, self.noise, evaluated, True)
         n0, d = pointGrid.shape
-        if n0 + m > 2048:
-            raise ValueError("3 d + m exceeds GP_SMALL_MAX_N")
-        batch = SmallModelBatch(default_context(), pointGrid, hp.toDenseVector()[None, :], Y=evaluated[:, None],
-                                sigma_noise=self.noise, capacity=n0 + m)
+        ctx, theta = default_context(), hp.toDenseVector()
+        # up to GP_SMALL_MAX_N observations the batched small-n path with its O(n^2) append; past it the large model (gp_fit_rbf,
+        # gp_model_maximize_ucb), refitted per accepted point
+        cap = min(n0 + m, GP_SMALL_MAX_N)
+        batch = SmallModelBatch(ctx, pointGrid, theta[None, :], Y=evaluated[:, None], sigma_noise=self.noise, capacity=cap) if n0 <= cap else None
+        large = None if batch is not None else RegressionModel(ctx, pointGrid, evaluated, theta, sigma_noise=self.noise)
         points, values = [row.copy() for row in pointGrid], list(evaluated)
         try:
             for _ in range(m):
                 P = np.asarray(points)
                 mean, cov = meanAndVarOfData(P)                                   # :52-53
                 starts = self._rng.multivariate_normal(mean, cov, size=c, method="svd").reshape(c, d)
-                best_x, best_ucb, _ = batch.maximize_ucb(starts, k, max_iter=10, history=4)   # BreezeLbfgsOptimizer() default maxIter = 10
+                surrogate = batch if batch is not None else large
+                best_x, best_ucb, _ = surrogate.maximize_ucb(starts, k, max_iter=10, history=4)   # BreezeLbfgsOptimizer() default maxIter = 10
                 if not np.isfinite(best_ucb):
                     best_x = self._rng.multivariate_normal(mean, cov, method="svd")          # :64
                 try:
                     y = float(func(best_x))
-                    batch.append(best_x, [y])                                     # :66-69 without the O(n^3) refit
+                    if batch is not None and len(points) < cap:
+                        batch.append(best_x, [y])                                 # :66-69 without the O(n^3) refit
+                    else:                                                         # :51 as the reference does it: a refit on the extended sets
+                        refit = RegressionModel(ctx, np.vstack([P, np.asarray(best_x)[None, :]]), np.append(values, y), theta, sigma_noise=self.noise)
+                        for old in (batch, large):
+                            if old is not None:
+                                old.close()
+                        batch, large = None, refit
                     points.append(np.array(best_x))
                     values.append(y)
                 except Exception:                                                  # :70-72: a failed evaluation keeps the old sets
                     pass
         finally:
-            batch.close()
+            for old in (batch, large):
+                if old is not None:
+                    old.close()
         values = np.asarray(values)
         i = int(np.argmax(values))                                                 # first maximum, like the fold at :73-78
         return np.array(points[i]), float(values[i])

@@ -61,7 +61,7 @@ const char *gp_last_error(const gp_ctx *ctx);
  * while set, every launch of those kernel classes is bracketed by events.  gp_ctx_profile_read
  * returns launches, total ms and the algorithmic work (flops or bytes) the launches of one class
  * carried, then resets that class's counters.  mask = 0 switches profiling off. */
-enum { GP_PROF_OFF = 0, GP_PROF_GEMM = 1, GP_PROF_SYRK = 2, GP_PROF_GRAM = 3, GP_PROF_TRSM = 4, GP_PROF_POTRF_DIAG = 5, GP_PROF_PANEL_UPD = 6, GP_PROF_NCLASSES = 7 };
+enum { GP_PROF_OFF = 0, GP_PROF_GEMM = 1, GP_PROF_SYRK = 2, GP_PROF_GRAM = 3, GP_PROF_TRSM = 4, GP_PROF_POTRF_DIAG = 5, GP_PROF_PANEL_UPD = 6, GP_PROF_PREDICT_GRAD = 7 /* the gradient pass of gp_predict_grad_dev; work = bytes read */, GP_PROF_NCLASSES = 8 };
 gp_status gp_ctx_profile(gp_ctx *ctx, int mask);
 gp_status gp_ctx_profile_read(gp_ctx *ctx, int which, int64_t *launches, double *total_ms, double *work);
 /* Look-ahead of the blocked Cholesky (far part of an outer trailing update on the context's CU-masked side stream, under the next
@@ -143,6 +143,29 @@ void gp_model_destroy(gp_model *model);
 gp_status gp_predict(gp_model *model, const double *Xs, int m, int ldxs, double *mean, double *var_diag, double *cov, int ldc);
 /* device-resident variant: dXs (m x d), dmean[m], dvar[m] in HBM; asynchronous. */
 gp_status gp_predict_dev(gp_model *model, const double *dXs, int m, int ldxs, double *dmean, double *dvar);
+/* The posterior AND its gradients w.r.t. the test points, for an ARD-RBF model from gp_fit_rbf / gp_fit_rbf_dev of any size -- what
+ * GPOptimizer.maximizeUCB (gp/optimization/GPOptimizer.scala:88-106) takes from computePosterior (:91) and
+ * GaussianRbfKernel.gradient(afterFirstArg = true) (utils/KernelRequisites.scala:95-107) one candidate at a time:
+ * D_ijk = -k*_ij (x*_ik - X_jk) / l_k^2, gmean[i,k] = sum_j D_ijk alpha_j (:97-99), gvar[i,k] = -2 sum_j D_ijk (K^-1 k*_i)_j (:100-101).
+ * mean[m], var[m] as gp_predict_dev (the same code: the same bits); gmean, gvar: m x d column-major, leading dimension ldg >= m;
+ * var / gmean / gvar optional (NULL).  Test points go through in batches of batch_rows (rounded down to a multiple of 128, at least 128;
+ * 0 = the rule of gp_predict_dev, GPCORE_PREDICT_BATCH included), so m is unbounded.  GP_EINVAL for a model from gp_fit_from_gram or
+ * gp_fit_co2; GP_ENOTPD if the model's last (re)fit failed.  After a gp_model_refit_dev the first call synchronises once to learn
+ * that, exactly as gp_model_status would, and the model remembers the answer until its next refit.  Like gp_model_status it reads
+ * the CONTEXT's status word, which every factorisation on the context resets: read a refitted model's status (gp_model_status, or its
+ * first gradient call) BEFORE another model is fitted or refitted on the same context, or the answer is that other model's.
+ * m == 0: GP_OK, nothing written. */
+gp_status gp_predict_grad_dev(gp_model *model, const double *dXs, int m, int ldxs, int batch_rows, double *dmean, double *dvar, double *dgmean, double *dgvar, int ldg);   /* asynchronous */
+gp_status gp_predict_grad(gp_model *model, const double *Xs, int m, int ldxs, double *mean, double *var, double *gmean, double *gvar, int ldg);
+/* GPOptimizer.maximizeUCB's objective (gp/optimization/GPOptimizer.scala:88-106) on such a model at m candidate points, argument for
+ * argument the layout of gp_small_ucb: value[i] = mean + kappa*sqrt(var), grad[i*d + k] = gmean + kappa / (2 sqrt(var)) * gvar.
+ * Where rounding leaves var[i] <= 0 (a candidate on a training point of a model with next to no noise) value[i] and its gradient are
+ * not finite, as gp_small_ucb's are: no status is raised, gp_model_maximize_ucb skips such evaluations. */
+gp_status gp_model_ucb(gp_model *model, const double *Xs, int m, int ldxs, double kappa, double *value, double *grad);
+/* The c L-BFGS runs of one GP-UCB iteration (GPOptimizer.scala:55-63; BreezeLbfgsOptimizer m = history, maxIter = max_iter,
+ * optimization/Optimization.scala:30-63) on such a model: gp_small_maximize_ucb's lockstep driver (the same host loop) over
+ * gp_model_ucb.  starts is c x d (leading dimension lds); best_x[d], *best_val: the best point and UCB value any evaluation saw. */
+gp_status gp_model_maximize_ucb(gp_model *model, const double *starts, int c, int lds, double kappa, int max_iter, int history, double *best_x, double *best_val, int *evals_out);
 /* GpPredictor.computePosterior(trainingData, testData, l, alphaVec), gp/regression/GpPredictor.scala:45-58, for a factor the
  * CALLER holds (the entry GP-UCB, gp/optimization/GPOptimizer.scala:91, and the GP-UKF,
  * dynamicalsystems/filtering/GPUnscentedKalmanFilter.scala:78-87,141-142, use): mean = K* alpha,
