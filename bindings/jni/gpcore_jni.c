@@ -504,6 +504,17 @@ JNIEXPORT jdouble JNICALL Java_gpcore_Native_modelMaximizeUcb(JNIEnv *env, jclas
     return best;
 }
 
+/* gp_model_append: k new observations (xNew k x d column-major, leading dimension k) onto the large model, GPOptimizer.scala:51,64-67 without the refit */
+JNIEXPORT void JNICALL Java_gpcore_Native_modelAppend(JNIEnv *env, jclass k, jlong h, jlong m, jdoubleArray xNew, jint kk, jint d, jdoubleArray yNew) {
+    double *X = in_d(env, xNew, 0, (jsize)kk * d), *Y = X ? in_d(env, yNew, 0, kk) : NULL;
+    if (Y) {
+        int info = 0;
+        gp_status st = gp_model_append(MODEL(m), X, kk, kk, Y, &info);
+        if (st != GP_OK) throw_for(env, CTX(h), st, info);
+    }
+    free(Y); free(X);
+}
+
 /* ---- Co2Kernel (Co2Prediction.scala:29-137) ---- */
 JNIEXPORT jlong JNICALL Java_gpcore_Native_fitCo2(JNIEnv *env, jclass k, jlong h, jdoubleArray x, jint n, jdoubleArray y, jdoubleArray theta,
                                                   jdouble sigmaNoiseOrNaN) {

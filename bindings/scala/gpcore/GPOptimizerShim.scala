@@ -22,7 +22,7 @@ import utils.StatsUtils._
   *     objective of :88-106 evaluated by ONE launch per trial point (gp_small_ucb) instead of computePosterior + two derivative
   *     matrices + a product with L^-1 on the host;
   *   - past GP_SMALL_MAX_N observations the same two paths run on the large regression model (gp_model_maximize_ucb / gp_model_ucb
-  *     over gp_predict_grad), refitted per accepted point.
+  *     over gp_predict_grad), fitted once and extended per accepted point in O(n^2) (gp_model_append).
   * `KernelFunc.gradient` is implemented by GaussianRbfKernel only (Co2Kernel's is `???`, Co2Prediction.scala:62-64), so that is
   * the kernel this class has ever worked with; anything else fails the `require` below instead of the reference's NotImplementedError. */
 class GPOptimizer(@BeanProperty var gpPredictor: GpPredictor, noise: Option[Double], gradientOptimizer: GradientBasedOptimizer) {
@@ -47,8 +47,8 @@ class GPOptimizer(@BeanProperty var gpPredictor: GpPredictor, noise: Option[Doub
     val (n0, d) = (pointGrid.rows, pointGrid.cols)
 
     // the point set and its values grow on the host exactly as in the reference (:47-72); the model grows on the device: up to
-    // GP_SMALL_MAX_N observations as a gp_small with its O(n^2) append, above that as a large model (gp_fit_rbf) refitted per
-    // accepted point, which is what the reference does at every size (:51)
+    // GP_SMALL_MAX_N observations as a gp_small with its O(n^2) append, above that as a large model (gp_fit_rbf, fitted once when the
+    // gp_small is full) with ITS O(n^2) append (gp_model_append), where the reference refits at every size (:51)
     var points = Vector.tabulate(n0)(i => pointGrid(i, ::).t.toArray)
     var values = evaluatedPointGrid.toArray.toVector
     val theta = hp.toDenseVector.toArray
@@ -72,20 +72,20 @@ class GPOptimizer(@BeanProperty var gpPredictor: GpPredictor, noise: Option[Doub
         val starts = Array.fill(c)(sampler.sample.toArray)                                  // :57, one start per L-BFGS run
         val (biggestUcb, found) = maximizeUcbOnDevice(small, large, starts, d, k)
         val biggestUcbPoint = if (found.isEmpty || biggestUcb.isNaN) sampler.sample.toArray else found.get   // :64
-        try {
-          val evaluated = func(biggestUcbPoint)                                             // :66-69
+        val evaluatedOpt =
+          try Some(func(biggestUcbPoint))                                                   // :66-69
+          catch { case _: Exception => None }                                               // :70-72: the sets stay as they were
+        evaluatedOpt.foreach { evaluated =>
           if (small != 0L && points.length < capacity)
             rethrowNotPd { Native.smallAppend(ctx, small, d, 1, biggestUcbPoint, Array(evaluated)) }
-          else {
-            val refit = fitLarge(points :+ biggestUcbPoint, values :+ evaluated)
-            if (small != 0L) { Native.smallDestroy(small); small = 0L }
-            if (large != 0L) Native.modelDestroy(large)
-            large = refit
+          else if (large != 0L)
+            rethrowNotPd { Native.modelAppend(ctx, large, biggestUcbPoint, 1, d, Array(evaluated)) }
+          else {                                                                            // the gp_small is full: ONE fit of the large model
+            large = fitLarge(points :+ biggestUcbPoint, values :+ evaluated)
+            Native.smallDestroy(small); small = 0L
           }
           points = points :+ biggestUcbPoint
           values = values :+ evaluated
-        } catch {
-          case _: Exception =>                                                              // :70-72: the sets stay as they were
         }
       }
     } finally {

@@ -55,6 +55,7 @@ object Native {
   // the same objective and optimiser on the large regression model (fitRbf): no limit on n
   @native def modelUcb(ctx: Long, model: Long, xs: Array[Double], xsoff: Int, m: Int, d: Int, ldxs: Int, kappa: Double, value: Array[Double], grad: Array[Double]): Unit
   @native def modelMaximizeUcb(ctx: Long, model: Long, starts: Array[Double], c: Int, d: Int, kappa: Double, maxIter: Int, history: Int, bestX: Array[Double]): Double
+  @native def modelAppend(ctx: Long, model: Long, xNew: Array[Double], k: Int, d: Int, yNew: Array[Double]): Unit
   // Co2Kernel
   @native def gramCo2(ctx: Long, x: Array[Double], n: Int, theta: Array[Double], out: Array[Double]): Unit
   @native def dgramCo2(ctx: Long, x: Array[Double], n: Int, theta: Array[Double], pos: Int, out: Array[Double]): Unit

@@ -53,6 +53,8 @@ SIGNATURES = {
     "gp_fit_from_gram": (_i, [_vp, _dp, _i, _i, _dp, C.POINTER(_vp), _ip]),
     "gp_model_refit_dev": (_i, [_vp, _dp, _d]),
     "gp_model_status": (_i, [_vp, _ip]),
+    "gp_model_append_dev": (_i, [_vp, _vp, _i, _i, _vp, _ip]),
+    "gp_model_append": (_i, [_vp, _dp, _i, _i, _dp, _ip]),
     "gp_model_get": (_i, [_vp, _i, _dp, _i]),
     "gp_model_destroy": (None, [_vp]),
     "gp_predict": (_i, [_vp, _dp, _i, _i, _dp, _dp, _dp, _i]),

@@ -378,6 +378,26 @@ class RegressionModel:
         self.ctx.check(self.ctx._lib.gp_model_get(self.h, L.GP_GET_LML, L.dptr(out), 1))
         return float(out[0])
 
+    def append(self, X_new, y_new):
+        """gp_model_append: extend the fitted model by one point (d values) or k points (k x d) in O(k n^2) -- afterwards it is the
+        model a fit on the extended data would give.  NotPositiveDefinite (.info = the pivot in that fit's numbering) leaves the model
+        at the size it had before the failing piece of at most 128 rows; self.n says which."""
+        if self.d < 1:
+            X_new = L.f64(np.asarray(X_new, dtype=np.float64).reshape(-1, 1))     # refused by the library, with its message
+        else:
+            X_new = L.f64(np.asarray(X_new, dtype=np.float64).reshape(-1, self.d))
+        y_new = L.f64(np.asarray(y_new, dtype=np.float64).reshape(-1))
+        k = X_new.shape[0]
+        if y_new.size != k:
+            raise ValueError("Number of objects in training data matrix should be equal to targets vector length")
+        info = C.c_int()
+        st = self.ctx._lib.gp_model_append(self.h, L.dptr(X_new), k, max(k, 1), L.dptr(y_new), C.byref(info))
+        if st == L.GP_OK:
+            self.n += k
+        elif st == L.GP_ENOTPD:      # pieces end on multiples of 128: everything before the failing pivot's block is in
+            self.n = max(self.n, (info.value - 1) // 128 * 128)
+        self.ctx.check(st, info.value)
+
     def predict(self, Xs, full_cov=False):
         Xs = L.f64(Xs)
         m = Xs.shape[0]

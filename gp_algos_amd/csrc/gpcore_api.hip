@@ -662,7 +662,7 @@ void solve_rows_upper(gp_ctx *ctx, double *Vt, int mp, const double *U, int np, 
 gp_status model_alloc(gp_ctx *ctx, int n, int d, bool has_x, gp_model **out) {
     gp_model *m = new (std::nothrow) gp_model();
     if (!m) return GP_ENOMEM;
-    m->ctx = ctx; m->n = n; m->d = d; m->np = gp_pad(n); m->ldl = m->np + GP_NB; m->has_x = has_x;
+    m->ctx = ctx; m->n = n; m->ldx = n; m->d = d; m->np = gp_pad(n); m->ldl = m->np + GP_NB; m->has_x = has_x;
     const size_t np = m->np;
     hipError_t e = hipSuccess;
     if (has_x) e = hipMalloc(&m->dX, sizeof(double) * (size_t)n * d);
@@ -1202,7 +1202,7 @@ gp_status gp_model_refit_dev(gp_model *m, const double *theta, double sigma_nois
     m->sigma_noise = sigma_noise;
     gp_prof_begin(ctx, GP_PROF_GRAM);
     if (m->kind == 1) gpk_co2_gram(ctx->stream, m->dX, m->n, m->dX, m->n, theta, 0, m->dL, m->ldl, 1, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise);
-    else gpk_gram_sym(ctx->stream, m->dX, m->n, m->d, m->n, theta, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
+    else gpk_gram_sym(ctx->stream, m->dX, m->n, m->d, m->ldx, theta, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m->n * (m->n + 1.0) / 2.0 + 8.0 * m->n * m->d);
     model_factor(m);
     GP_LAUNCH_CHECK(ctx);
@@ -1363,7 +1363,9 @@ void gp_model_destroy(gp_model *m) {
 }
 
 // posterior at m test points already in HBM: mean, diagonal variance; Vt stays in the workspace
-static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs, double *dmean, double *dvar, double **vt_out, int *mp_out) {
+// small_form: never the folded factor Lw (gp_model_append_dev: a 128-row solve must not build it)
+static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs, double *dmean, double *dvar, double **vt_out, int *mp_out,
+                              bool small_form = false) {
     gp_ctx *ctx = mdl->ctx;
     hipStream_t s = ctx->stream;
     const int n = mdl->n, np = mdl->np, mp = gp_pad(m);
@@ -1378,7 +1380,7 @@ static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs,
     }
     gp_prof_begin(ctx, GP_PROF_GRAM);
     if (mdl->kind == 1) gpk_co2_gram(s, dXs, m, mdl->dX, n, mdl->theta.data(), 0, Vt, mp, 0, 1, 0.0);
-    else gpk_gram_cross(s, dXs, m, ldxs, mdl->dX, n, n, mdl->d, mdl->theta.data(), Vt, mp, gp_gram_flag(ctx), mdl->dcen);
+    else gpk_gram_cross(s, dXs, m, ldxs, mdl->dX, n, mdl->ldx, mdl->d, mdl->theta.data(), Vt, mp, gp_gram_flag(ctx), mdl->dcen);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m * (double)n + 8.0 * (m + n) * mdl->d);
     // sumsq and the mean accumulate inside the row-panel solves: var = kss - |v|^2, mean = v . (L^-1 y)  (= K* alpha)
     double *dots = partial;
@@ -1386,7 +1388,7 @@ static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs,
     GP_HIP(ctx, hipMemsetAsync(dots, 0, sizeof(double) * mp, s));
     const double *Lw = nullptr;
     const bool use_lw = [] { const char *e = getenv("GPCORE_POSTERIOR_LW"); return !e || atoi(e) != 0; }();
-    if (use_lw && mp / GP_NB >= rows_left_min()) {   // large batch: fold the panel solves into the GEMMs (see build_lw)
+    if (use_lw && !small_form && mp / GP_NB >= rows_left_min()) {   // large batch: fold the panel solves into the GEMMs (see build_lw)
         if (!mdl->dLw) {
             hipError_t e = hipMalloc(&mdl->dLw, sizeof(double) * (size_t)np * np);
             if (e != hipSuccess) { mdl->dLw = nullptr; GP_SET_ERR(ctx, "hipMalloc(Lw, n=%d) failed: %s", n, hipGetErrorString(e)); return GP_ENOMEM; }
@@ -1531,7 +1533,7 @@ gp_status gp_predict_grad_dev(gp_model *mdl, const double *dXs, int m, int ldxs,
         GP_REQUIRE(ctx, gpk_predict_grad_partials(mb, n, d) <= need, "internal: gradient scratch smaller than this batch needs");
         if (dgvar) solve_rows_upper(ctx, Vt, mp, mdl->dLt, np, np);
         gp_prof_begin(ctx, GP_PROF_PREDICT_GRAD);
-        gpk_predict_grad(s, dgvar ? Vt : nullptr, mp, dXs + lo, mb, ldxs, mdl->dX, n, n, d, mdl->theta.data(), mdl->dalpha, partials,
+        gpk_predict_grad(s, dgvar ? Vt : nullptr, mp, dXs + lo, mb, ldxs, mdl->dX, n, mdl->ldx, d, mdl->theta.data(), mdl->dalpha, partials,
                          dgmean ? dgmean + lo : nullptr, dgvar ? dgvar + lo : nullptr, ldg);
         // bytes it must read: W once (when gvar is asked for), the test points, and X and alpha once per 64 test points
         gp_prof_end(ctx, GP_PROF_PREDICT_GRAD, 8.0 * ((dgvar ? (double)mb * n : 0.0) + (double)mb * d + (double)((mb + 63) / 64) * n * (d + 1.0)));
@@ -1589,6 +1591,158 @@ gp_status gp_model_maximize_ucb(gp_model *mdl, const double *starts, int c, int 
     return gpi_ucb_lbfgs_lockstep(mdl->d, starts, c, lds, max_iter, history,
                                   [&](const double *pts, int count, double *val, double *grd) { return gp_model_ucb(mdl, pts, count, count, kappa, val, grd); },
                                   best_x, best_val, evals_out);
+}
+
+// ---- appending observations to a fitted model (GPOptimizer.scala:51,64-67 without the refit) ------------------------------------
+// np -> np + 128 when n sits on a block boundary: every padded buffer moves to its new size with one strided copy (the factor's
+// leading dimension changes, so its strip y^T / t^T moves from row np to row np + 128), the new block gets what gpk_pad_identity
+// and a fit would leave there.  Lw / L^T grow too while they are valid (their new block row is [0 | I]), otherwise they are dropped.
+static gp_status model_grow(gp_model *m) {
+    gp_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    const int np = m->np, nq = np + GP_NB, ldq = nq + GP_NB;
+    const bool keep_lw = m->dLw && m->lw_valid, keep_lt = m->dLt && m->lt_valid;
+    double *nb[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // L, y, alpha, dinv, tmp, Lw, Lt
+    const size_t cnt[7] = {(size_t)ldq * nq, (size_t)nq, (size_t)nq, (size_t)nq * 16, (size_t)2 * nq, keep_lw ? (size_t)nq * nq : 0, keep_lt ? (size_t)nq * nq : 0};
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 7 && e == hipSuccess; ++q) {
+        if (!cnt[q]) continue;
+        e = hipMalloc(&nb[q], sizeof(double) * cnt[q]);
+        if (e == hipSuccess) e = hipMemsetAsync(nb[q], 0, sizeof(double) * cnt[q], s);
+    }
+    if (e != hipSuccess) {
+        for (double *p : nb) if (p) (void)hipFree(p);
+        GP_SET_ERR(ctx, "growing the model to %d padded rows failed: %s", nq, hipGetErrorString(e));
+        return GP_ENOMEM;
+    }
+    gpk_copy_2d(s, nb[0], ldq, m->dL, m->ldl, np, np);
+    gpk_copy_strided(s, nb[0] + nq, (size_t)ldq, m->dL + np, (size_t)m->ldl, np);
+    gpk_pad_identity(s, nb[0], np, nq, ldq);
+    gpk_copy_2d(s, nb[1], nq, m->dy, np, np, 1);
+    gpk_copy_2d(s, nb[2], nq, m->dalpha, np, np, 1);
+    gpk_copy_2d(s, nb[3], nq * 16, m->ddinv, np * 16, np * 16, 1);
+    gpk_tile_inverses(s, nb[0] + (size_t)np + (size_t)np * ldq, GP_NB, ldq, nb[3] + (size_t)np * 16);     // of the identity block
+    gpk_copy_2d(s, nb[4], nq, m->dtmp, np, np, 1);
+    if (keep_lw) {
+        gpk_copy_2d(s, nb[5], nq, m->dLw, np, np, np);
+        gpk_set_identity(s, nb[5] + (size_t)np + (size_t)np * nq, GP_NB, nq);
+    }
+    if (keep_lt) {
+        gpk_copy_2d(s, nb[6], nq, m->dLt, np, np, np);
+        gpk_set_identity(s, nb[6] + (size_t)np + (size_t)np * nq, GP_NB, nq);
+    }
+    GP_LAUNCH_CHECK(ctx);
+    GP_HIP(ctx, hipStreamSynchronize(s));
+    double **old[7] = {&m->dL, &m->dy, &m->dalpha, &m->ddinv, &m->dtmp, &m->dLw, &m->dLt};
+    for (int q = 0; q < 7; ++q) {
+        if (*old[q]) (void)hipFree(*old[q]);
+        *old[q] = nb[q];
+    }
+    m->lw_valid = keep_lw;
+    m->lt_valid = keep_lt;
+    m->np = nq;
+    m->ldl = ldq;
+    return GP_OK;
+}
+
+// room for `rows` training inputs: dX is re-laid with the padded size as its leading dimension (n d doubles, once per 128 appended rows)
+static gp_status model_reserve_x(gp_model *m, int rows) {
+    if (m->ldx >= rows) return GP_OK;
+    gp_ctx *ctx = m->ctx;
+    const int ld = gp_pad(rows);
+    double *nx = nullptr;
+    hipError_t e = hipMalloc(&nx, sizeof(double) * (size_t)ld * m->d);
+    if (e != hipSuccess) { GP_SET_ERR(ctx, "growing the training inputs to %d rows failed: %s", ld, hipGetErrorString(e)); return GP_ENOMEM; }
+    gpk_copy_2d(ctx->stream, nx, ld, m->dX, m->ldx, m->n, m->d);
+    GP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(m->dX);
+    m->dX = nx;
+    m->ldx = ld;
+    return GP_OK;
+}
+
+// One piece: k <= 128 - n % 128 new rows, all inside one 128-row block of the factor.
+static gp_status append_piece(gp_model *m, const double *dXn, int k, int ldxn, const double *dyn, int *info) {
+    gp_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    if (m->n == m->np) GP_TRY(model_grow(m));
+    GP_TRY(model_reserve_x(m, m->n + k));
+    const int n = m->n, np = m->np, d = m->d, b0 = n / GP_NB * GP_NB;
+    gpk_copy_2d(s, m->dX + n, m->ldx, dXn, ldxn, k, d);        // rows n .. of dX: nobody reads them before the piece is committed
+    double *Knn, *dots, *Vt = nullptr;
+    int mp = 0;
+    GP_TRY(ws_get(ctx, WS_B, sizeof(double) * GP_NB * GP_NB, &Knn));
+    GP_TRY(ws_get(ctx, WS_C, sizeof(double) * GP_NB, &dots));
+    // the posterior's own row solve at the new points: V = K_new,old L^-T (zeros in the pad columns) and dots = V t
+    GP_TRY(predict_core(m, m->dX + n, k, m->ldx, dots, nullptr, &Vt, &mp, true));
+    gpk_gram_sym(s, m->dX + n, k, d, m->ldx, m->theta.data(), Knn, GP_NB, 0, std::isnan(m->sigma_noise) ? 0.0 : m->sigma_noise, gp_gram_flag(ctx), m->dcen);
+    GP_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
+    gpk_model_append(s, Vt, mp, Knn, GP_NB, dyn, dots, m->dL, m->ldl, m->ddinv, m->dtmp, m->dy, ctx->d_info, n, k, np);
+    GP_LAUNCH_CHECK(ctx);
+    int h = 0;
+    GP_TRY(read_info(ctx, &h));      // the one synchronisation of a piece: nothing below may run on a border that was not committed
+    if (h) {
+        GP_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));      // the factor in dL is the good one of n rows: gp_model_status keeps saying so
+        if (info) *info = h;
+        GP_SET_ERR(ctx, "matrix not positive definite at pivot %d", h);
+        return GP_ENOTPD;
+    }
+    m->n = n + k;
+    gpk_centroid(s, m->dX, m->n, d, m->ldx, m->dcen);
+    gpk_lml(s, m->dL, m->n, m->ldl, m->dtmp, m->dlml);
+    m->alpha_valid = false;
+    if (m->dLw && m->lw_valid) {
+        // only block row b of Lw = L_bb^-1 [ -L_b,<b | I ] changed: the single-block case of build_lw (negated transpose, ONE 128-column
+        // panel solve against L_bb, transpose back)
+        const int rows = b0 + GP_NB;
+        double *X;
+        GP_TRY(ws_get(ctx, WS_D, sizeof(double) * (size_t)rows * GP_NB, &X));
+        gpk_transpose(s, X, rows, m->dL + b0, m->ldl, GP_NB, b0, -1.0);
+        gpk_set_identity(s, X + b0, GP_NB, rows);
+        gp_prof_begin(ctx, GP_PROF_TRSM);
+        gpk_trsm_panel128(s, X, rows, rows, m->dL + (size_t)b0 + (size_t)b0 * m->ldl, m->ldl, m->ddinv + (size_t)b0 * 16, nullptr);
+        gp_prof_end(ctx, GP_PROF_TRSM, (double)rows * GP_NB * GP_NB);
+        gpk_transpose(s, m->dLw + b0, np, X, rows, rows, GP_NB);
+    }
+    if (m->dLt && m->lt_valid) gpk_transpose(s, m->dLt + (size_t)b0 * np, np, m->dL + b0, m->ldl, GP_NB, b0 + GP_NB);   // the block row of L, transposed
+    GP_LAUNCH_CHECK(ctx);
+    return GP_OK;
+}
+
+static gp_status append_checks(gp_model *m, const void *x, int k, int ldx, const void *y, int *info) {
+    if (!m) return GP_EINVAL;
+    gp_ctx *ctx = m->ctx;
+    if (info) *info = 0;
+    GP_REQUIRE(ctx, m->has_x && m->kind == 0, "appending needs an ARD-RBF model fitted from training inputs (gp_fit_rbf), not one from a Gram matrix or gp_fit_co2");
+    GP_REQUIRE(ctx, x && y, "null pointer");
+    GP_REQUIRE(ctx, k >= 1 && ldx >= k, "bad dimensions (k >= 1, ldx >= k)");
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!m->info_known) {
+        const gp_status st = gp_model_status(m, nullptr);
+        if (st != GP_OK && st != GP_ENOTPD) return st;
+    }
+    GP_REQUIRE(ctx, m->last_info == 0, "the model's last (re)fit failed: there is no factor to extend");
+    return GP_OK;
+}
+
+gp_status gp_model_append_dev(gp_model *m, const double *dX_new, int k, int ldx, const double *dy_new, int *info) {
+    GP_TRY(append_checks(m, dX_new, k, ldx, dy_new, info));
+    for (int off = 0; off < k;) {
+        const int kk = std::min(k - off, GP_NB - m->n % GP_NB);       // no piece crosses a 128-row block of the factor
+        GP_TRY(append_piece(m, dX_new + off, kk, ldx, dy_new + off, info));
+        off += kk;
+    }
+    return GP_OK;
+}
+
+gp_status gp_model_append(gp_model *m, const double *X_new, int k, int ldx, const double *y_new, int *info) {
+    GP_TRY(append_checks(m, X_new, k, ldx, y_new, info));
+    gp_ctx *ctx = m->ctx;
+    double *dbuf;
+    GP_TRY(ws_get(ctx, WS_A, sizeof(double) * (size_t)k * (m->d + 1), &dbuf));
+    GP_TRY(upload_2d(ctx, dbuf, k, X_new, ldx, k, m->d));
+    GP_TRY(upload_2d(ctx, dbuf + (size_t)k * m->d, k, y_new, k, k, 1));
+    return gp_model_append_dev(m, dbuf, k, k, dbuf + (size_t)k * m->d, info);
 }
 
 }  // extern "C"

@@ -55,7 +55,8 @@ struct gp_model {
     int ldl = 0;                     // leading dimension of dL = np + GP_NB: one extra row strip carries y^T through the factorisation
     bool has_x = false;              // false for gp_fit_from_gram
     int kind = 0;                    // kernel the model rebuilds Gram matrices with: 0 = ARD-RBF (theta = d + 2), 1 = Co2Kernel (d = 1, theta = 11)
-    double *dX = nullptr;            // n x d, ld = n
+    double *dX = nullptr;            // n x d, ld = ldx
+    int ldx = 0;                     // leading dimension of dX: n as fitted, the padded size once gp_model_append_dev has made room
     double *dcen = nullptr;          // d: centroid of the rows of dX (centre of the matrix-core Gram forms), set with dX
     double *dy = nullptr;            // np
     double *dL = nullptr;            // (np + GP_NB) x np, ld = ldl; row np holds y^T -> (L^-1 y)^T
@@ -139,7 +140,7 @@ void gpk_zero_upper(hipStream_t s, double *A, int n, int lda);
 void gpk_fill(hipStream_t s, double *p, size_t count, double v);
 // X (M x 128) <- X * Ukk^{-T} with Ukk UPPER triangular (back substitution per row)
 void gpk_trsm_panel_upper(hipStream_t s, double *X, int M, int ldx, const double *Ukk, int ldu);
-void gpk_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int rows, int cols);
+void gpk_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int rows, int cols, double sign = 1.0);   // dst = sign * src^T
 // stage = 1: dst (upper form) <- -(strict block-lower part of src)^T with identity 128-blocks on the diagonal;
 // stage = 0: dst (lower form) <- (upper form src)^T, block-lower part and diagonal blocks only.
 void gpk_lw_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int np, int stage);
@@ -185,6 +186,12 @@ void gpk_trsm_panel128(hipStream_t s, double *X, int M, int ldx, const double *L
 void gpk_fwd_step(hipStream_t s, const double *L, int ldl, const double *dinv_k, double *t, double *sol, int k0, int r);
 void gpk_bwd_step(hipStream_t s, const double *L, int ldl, const double *dinv_k, double *t, double *sol, int k0);
 void gpk_tile_inverses(hipStream_t s, const double *L, int np, int ldl, double *dinv);
+// the border of gp_model_append_dev, one workgroup (kernels_diag.hip model_append_kernel): k <= 128 - n % 128 new rows.  Vt (ld ldv >= 128): the row
+// solve K_new,old L^-T, zeros from column n on and in rows >= k; Knn (ld ldk): the new points' Gram block, lower; dots[k] = V t.  On success rows
+// n .. n+k-1 of L, the strip (row np), tvec, yvec and the touched tiles of dinv are written; on a pivot that is not positive only *d_info (its
+// 1-based index in the extended matrix)
+void gpk_model_append(hipStream_t s, const double *Vt, int ldv, const double *Knn, int ldk, const double *ynew, const double *dots, double *L, int ldl,
+                      double *dinv, double *tvec, double *yvec, int *d_info, int n, int k, int np);
 // dst[j*dst_stride] = src[j*src_stride], j < count
 void gpk_copy_strided(hipStream_t s, double *dst, size_t dst_stride, const double *src, size_t src_stride, int count);
 

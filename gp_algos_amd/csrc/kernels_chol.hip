@@ -103,9 +103,9 @@ __global__ __launch_bounds__(64) void trsm_panel_upper_kernel(double *__restrict
     }
 }
 
-// dst (cols x rows) = src (rows x cols)^T, 64x64 LDS tiles, both sides coalesced
+// dst (cols x rows) = sign * src (rows x cols)^T, 64x64 LDS tiles, both sides coalesced
 __global__ __launch_bounds__(256) void transpose_kernel(double *__restrict__ dst, int ldd, const double *__restrict__ src, int lds,
-                                                        int rows, int cols) {
+                                                        int rows, int cols, double sign) {
     __shared__ double t[64][65];
     const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(double *__restrict__ dst
     __syncthreads();
     for (int q = ty; q < 64; q += 4) {
         int c = c0 + tx, r = r0 + q;   // dst(c, r) = src(r, c) = t[c-c0][r-r0]
-        if (r < rows && c < cols) dst[c + (size_t)r * ldd] = t[tx][q];
+        if (r < rows && c < cols) dst[c + (size_t)r * ldd] = sign * t[tx][q];
     }
 }
 
@@ -402,9 +402,9 @@ void gpk_trsm_panel_upper(hipStream_t s, double *X, int M, int ldx, const double
     if (M <= 0) return;
     hipLaunchKernelGGL(trsm_panel_upper_kernel, dim3((M + 63) / 64), dim3(64), 0, s, X, M, ldx, Ukk, ldu);
 }
-void gpk_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int rows, int cols) {
+void gpk_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int rows, int cols, double sign) {
     if (rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(transpose_kernel, dim3((rows + 63) / 64, (cols + 63) / 64), dim3(256), 0, s, dst, ldd, src, lds, rows, cols);
+    hipLaunchKernelGGL(transpose_kernel, dim3((rows + 63) / 64, (cols + 63) / 64), dim3(256), 0, s, dst, ldd, src, lds, rows, cols, sign);
 }
 void gpk_lw_transpose(hipStream_t s, double *dst, int ldd, const double *src, int lds, int np, int stage) {
     hipLaunchKernelGGL(lw_transpose_kernel, dim3(np / 64, np / 64), dim3(256), 0, s, dst, ldd, src, lds, stage);

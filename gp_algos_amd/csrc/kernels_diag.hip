@@ -993,9 +993,187 @@ __global__ __launch_bounds__(MEGA_THREADS, 1) void chol_mega_kernel(double *__re
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// The border of gp_model_append_dev: k <= 128 new observations onto a fitted model of n, all inside ONE 128-row block of the factor
+// (n mod 128 + k <= 128).  ONE workgroup.  V (k x n, rows of Vt, leading dimension ldv, zeros from column n on and in rows >= k) is
+// the row solve K_new,old L^-T of the posterior; Knn the new points' own Gram block (lower triangle, the diagonal gpk_gram_sym writes).
+//   S = Knn - V V^T        the k x k dot products over n on v_mfma_f64_16x16x4_f64, operands straight from L2: 16 x 16 tiles of the
+//                          lower triangle over the eight waves; up to six tiles (k <= 48) the n columns are also cut into chunks so
+//                          that all eight waves work, the partial sums meet in LDS in chunk order (no atomics: deterministic)
+//   S = C C^T              in LDS, potrf_block_body's micro-panel scheme on ceil(k / 16) tiles (identity in the pad of the last one)
+//                          with NOTHING stored: a pivot that is not positive (NaN included) ends the kernel with the factor, t, dinv
+//                          untouched and the pivot's 1-based index in the extended matrix in *info -- the single-guard rule
+//   t_new = C^-1 (y_new - V t)   V t = dots, the row solve's fused product; substitution in one wave
+//   commit                 rows n .. n+k-1 of L = [ V | C ] (replacing the pad identity), t into the strip (row np) and tvec, y_new into
+//                          yvec, and every 16 x 16 tile inverse the new rows touch, re-inverted whole from L (tile_inverse_kernel's
+//                          arithmetic) -- a tile that straddles old and new rows included.
+__global__ __launch_bounds__(64 * POTRF_WAVES) void model_append_kernel(const double *__restrict__ Vt, int ldv, const double *__restrict__ Knn, int ldk,
+                                                                        const double *__restrict__ ynew, const double *__restrict__ dots,
+                                                                        double *__restrict__ L, int ldl, double *__restrict__ dinv,
+                                                                        double *__restrict__ tvec, double *__restrict__ yvec, int *info,
+                                                                        int n, int k, int np) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    double *a = sm;                 // S, then C: column stride PLS
+    double *dv = sm + NB * PLS;     // inverse of the current diagonal tile
+    int *flag = reinterpret_cast<int *>(dv + 256);
+    double *rhs = dv + 256 + 8;     // NB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int nt = (k + 15) / 16, ntile = nt * (nt + 1) / 2;
+    if (tid == 0) *flag = 0;
+    // ---- S = Knn - V V^T ----
+    const int nch = ntile < POTRF_WAVES ? POTRF_WAVES / ntile : 1;      // column chunks per tile
+    const int nks = (n + 3) / 4, per = (nks + nch - 1) / nch;           // k-steps of four columns (columns n .. are zero)
+    double *part = a + 64 * PLS;                                        // nch > 1 means k <= 48: S lives in the first 48 columns
+    auto put = [&](int I, int J, int l, int rr, double sum) {
+        const int i = 16 * I + (l & 15), j = 16 * J + (l >> 4) + 4 * rr;
+        double v = (i == j) ? 1.0 : 0.0;                                // pad of the last tile
+        if (i < k && j < k) v = (i >= j) ? Knn[i + (size_t)j * ldk] - sum : 0.0;
+        a[i + j * PLS] = v;
+    };
+    for (int q = wave; q < ntile * nch; q += POTRF_WAVES) {
+        const int tile = q / nch, ch = q - tile * nch;
+        int I, J;
+        tri_coords(tile, I, J);
+        const int ks0 = ch * per, ks1 = min(nks, ks0 + per);
+        const double *pj = Vt + 16 * J + fr + (size_t)fg * ldv, *pi = Vt + 16 * I + fr + (size_t)fg * ldv;
+        double4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 8
+        for (int ks = ks0; ks < ks1; ++ks) acc = MFMA(pj[(size_t)ks * 4 * ldv], pi[(size_t)ks * 4 * ldv], acc);   // acc[rr]: (16 I + fr, 16 J + fg + 4 rr)
+        if (nch == 1) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) put(I, J, lane, rr, acc[rr]);
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) part[q * 256 + lane * 4 + rr] = acc[rr];
+        }
+    }
+    if (nch > 1) {
+        __syncthreads();
+        for (int e = tid; e < ntile * 256; e += 64 * POTRF_WAVES) {
+            const int tile = e >> 8;
+            int I, J;
+            tri_coords(tile, I, J);
+            double sum = 0.0;
+            for (int ch = 0; ch < nch; ++ch) sum += part[(tile * nch + ch) * 256 + (e & 255)];
+            put(I, J, (e >> 2) & 63, e & 3, sum);
+        }
+    }
+    if (tid < NB) rhs[tid] = (tid < k) ? ynew[tid] - dots[tid] : 0.0;
+    __syncthreads();
+    // ---- S = C C^T on chip: the loop of potrf_block_body over nt tiles, without its stores ----
+    for (int jb = 0; jb < nt; ++jb) {
+        const int c0 = jb * 16;
+        if (wave == 0) {
+            double row[16], x[16], sv[16];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) row[c] = a[(c0 + fr) + (c0 + c) * PLS];
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) sv[rr] = (rr == fr) ? 1.0 : 0.0;
+            double piv[16], guard = 0.0;
+            tile_chol_inv_cols<0>(row, sv, x, piv, guard);
+            if (lane < 16) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) a[(c0 + fr) + (c0 + c) * PLS] = row[c];
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) dv[rr + 16 * fr] = x[rr];
+            }
+            if (!(fabs(guard) < HUGE_VAL)) {     // a pivot was <= 0 or NaN: which one came first
+                int bad = 0;
+#pragma unroll
+                for (int j = 15; j >= 0; --j) if (!(piv[j] > 0.0)) bad = j + 1;
+                if (lane == 0) { atomicCAS(info, 0, n + c0 + bad); *flag = 1; }
+            }
+        }
+        __syncthreads();
+        if (*flag) return;          // nothing has been stored
+        const int T = nt - 1 - jb;
+        if (wave < T) {
+            const int r0 = c0 + 16 + 16 * wave;
+            double4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) acc = MFMA(dv[fr + 16 * (4 * ks + fg)], a[(r0 + fr) + (c0 + 4 * ks + fg) * PLS], acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[(r0 + fr) + (c0 + fg + 4 * r) * PLS] = acc[r];
+        }
+        __syncthreads();
+        const int nupd = T * (T + 1) / 2;
+        for (int q = wave; q < nupd; q += POTRF_WAVES) {
+            int bi, bj;
+            tri_coords(q, bi, bj);
+            const int ri = c0 + 16 + 16 * bi, rj = c0 + 16 + 16 * bj;
+            double4_t acc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = a[(ri + fr) + (rj + fg + 4 * r) * PLS];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) acc = MFMA(-a[(rj + fr) + (c0 + 4 * ks + fg) * PLS], a[(ri + fr) + (c0 + 4 * ks + fg) * PLS], acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[(ri + fr) + (rj + fg + 4 * r) * PLS] = acc[r];
+        }
+        __syncthreads();
+    }
+    // ---- t_new = C^-1 rhs: column-oriented substitution in wave 0, rows lane and lane + 64 ----
+    if (wave == 0) {
+        double r0 = rhs[lane], r1 = rhs[lane + 64];
+        for (int j = 0; j < k; ++j) {
+            const double v = (j < 64) ? __shfl(r0, j) : __shfl(r1, j - 64);
+            const double xj = v / a[j + j * PLS];
+            if (lane == j) r0 = xj;
+            if (lane + 64 == j) r1 = xj;
+            if (lane > j && lane < k) r0 = fma(-a[lane + j * PLS], xj, r0);
+            if (lane + 64 > j && lane + 64 < k) r1 = fma(-a[lane + 64 + j * PLS], xj, r1);
+        }
+        rhs[lane] = r0;
+        rhs[lane + 64] = r1;
+    }
+    __syncthreads();
+    // ---- commit ----
+    int kp2 = 1;
+    while (kp2 < k) kp2 <<= 1;
+    {
+        const int i = tid & (kp2 - 1), cstep = 64 * POTRF_WAVES / kp2;
+        if (i < k) {
+            for (int c = tid / kp2; c < n; c += cstep) L[(size_t)(n + i) + (size_t)c * ldl] = Vt[i + (size_t)c * ldv];
+            for (int j = tid / kp2; j < k; j += cstep) L[(size_t)(n + i) + (size_t)(n + j) * ldl] = (i >= j) ? a[i + j * PLS] : 0.0;
+        }
+    }
+    if (tid < k) {
+        const double tv = rhs[tid];
+        tvec[n + tid] = tv;
+        L[(size_t)np + (size_t)(n + tid) * ldl] = tv;
+        yvec[n + tid] = ynew[tid];
+    }
+    for (int g = n / 16 + wave; g <= (n + k - 1) / 16; g += POTRF_WAVES) {
+        const int R = 16 * g + fr;          // this lane's row of the tile, in the factor's numbering
+        double row[16], x[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const int Cc = 16 * g + c;
+            double v = (c == fr) ? 1.0 : 0.0;       // the pad identity below the new rows
+            if (c <= fr) {
+                if (R < n) v = L[(size_t)R + (size_t)Cc * ldl];
+                else if (R < n + k) v = (Cc < n) ? Vt[(R - n) + (size_t)Cc * ldv] : a[(R - n) + (Cc - n) * PLS];
+            }
+            row[c] = v;
+        }
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            double s = (rr == fr) ? 1.0 : 0.0;
+#pragma unroll
+            for (int kk = 0; kk < rr; ++kk) s = fma(-rl64(row[kk], rr), x[kk], s);
+            x[rr] = s / rl64(row[rr], rr);
+        }
+        if (lane < 16) {
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) dinv[(size_t)g * 256 + rr + 16 * fr] = x[rr];
+        }
+    }
+}
+
 }  // namespace
 
 static constexpr int POTRF_LDS = (NB * PLS + 256 + 8) * (int)sizeof(double);
+static constexpr int APPEND_LDS = POTRF_LDS + NB * (int)sizeof(double);
 static constexpr int TRSM_LDS = NB * XS * (int)sizeof(double);
 static constexpr int STEP_LDS = (NB * LS1 + 8 * 256 + NB + 16) * (int)sizeof(double);
 static constexpr int LINK_LDS = NB * LKS * (int)sizeof(double);
@@ -1009,6 +1187,7 @@ int gpk_init_diag_kernels() {
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(chol_mega_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MEGA_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(bwd_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(model_append_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, APPEND_LDS);
     return e == hipSuccess ? 0 : 1;
 }
 
@@ -1046,4 +1225,9 @@ void gpk_bwd_step(hipStream_t s, const double *L, int ldl, const double *dinv_k,
 }
 void gpk_tile_inverses(hipStream_t s, const double *L, int np, int ldl, double *dinv) {
     hipLaunchKernelGGL(tile_inverse_kernel, dim3(np / 16), dim3(64), 0, s, L, ldl, dinv);
+}
+void gpk_model_append(hipStream_t s, const double *Vt, int ldv, const double *Knn, int ldk, const double *ynew, const double *dots, double *L, int ldl,
+                      double *dinv, double *tvec, double *yvec, int *d_info, int n, int k, int np) {
+    hipLaunchKernelGGL(model_append_kernel, dim3(1), dim3(64 * POTRF_WAVES), APPEND_LDS, s, Vt, ldv, Knn, ldk, ynew, dots, L, ldl, dinv, tvec, yvec, d_info,
+                       n, k, np);
 }

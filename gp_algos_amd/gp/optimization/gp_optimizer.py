@@ -10,7 +10,8 @@ class GPOptimizer(gpPredictor, noise, gradientOptimizer) keeps the reference's c
 The random draws (initial grid, L-BFGS starting points) come from numpy instead of scala.util.Random(System.nanoTime()) /
 commons-math: the reference's trajectory is not reproducible by construction.
 Past GP_SMALL_MAX_N observations the loop continues on the large regression model (RegressionModel.maximize_ucb over
-gp_predict_grad), refitted per accepted point as the reference does."""
+gp_predict_grad): it is fitted once, when the small batch is full, and every accepted point after that is appended to it in O(n^2)
+(RegressionModel.append, gp_model_append) -- factor, t, LML and the cached matrices of the posterior are extended, nothing is refitted."""
 from dataclasses import dataclass
 from typing import Sequence
 
@@ -58,7 +59,7 @@ class GPOptimizer:
         n0, d = pointGrid.shape
         ctx, theta = default_context(), hp.toDenseVector()
         # up to GP_SMALL_MAX_N observations the batched small-n path with its O(n^2) append; past it the large model (gp_fit_rbf,
-        # gp_model_maximize_ucb), refitted per accepted point
+        # gp_model_maximize_ucb), fitted once and appended to per accepted point (gp_model_append)
         cap = min(n0 + m, GP_SMALL_MAX_N)
         batch = SmallModelBatch(ctx, pointGrid, theta[None, :], Y=evaluated[:, None], sigma_noise=self.noise, capacity=cap) if n0 <= cap else None
         large = None if batch is not None else RegressionModel(ctx, pointGrid, evaluated, theta, sigma_noise=self.noise)
@@ -76,12 +77,12 @@ class GPOptimizer:
                     y = float(func(best_x))
                     if batch is not None and len(points) < cap:
                         batch.append(best_x, [y])                                 # :66-69 without the O(n^3) refit
-                    else:                                                         # :51 as the reference does it: a refit on the extended sets
-                        refit = RegressionModel(ctx, np.vstack([P, np.asarray(best_x)[None, :]]), np.append(values, y), theta, sigma_noise=self.noise)
-                        for old in (batch, large):
-                            if old is not None:
-                                old.close()
-                        batch, large = None, refit
+                    elif large is not None:
+                        large.append(best_x, y)                                   # :51,64-67 on the large model, still O(n^2)
+                    else:                                                         # the small batch is full: ONE fit of the large model on the extended sets
+                        large = RegressionModel(ctx, np.vstack([P, np.asarray(best_x)[None, :]]), np.append(values, y), theta, sigma_noise=self.noise)
+                        batch.close()
+                        batch = None
                     points.append(np.array(best_x))
                     values.append(y)
                 except Exception:                                                  # :70-72: a failed evaluation keeps the old sets

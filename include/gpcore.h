@@ -132,6 +132,20 @@ gp_status gp_fit_from_gram(gp_ctx *ctx, const double *K, int n, int ldk, const d
 /* Re-fit an existing model in place (same n, d): no allocation, fully asynchronous. */
 gp_status gp_model_refit_dev(gp_model *model, const double *theta, double sigma_noise);
 gp_status gp_model_status(gp_model *model, int *info); /* syncs; GP_ENOTPD if the last (re)fit failed */
+/* GPOptimizer.scala:51,64-67 on the large model: extend the fitted model by k observations in O(k n^2);
+   the result is the model gp_fit_rbf would give on the extended data, to rounding.
+ * X_new is k x d (ldx >= k), any k >= 1; the call is carried out in pieces that do not cross a 128-row block of the factor.  Per piece: the
+ * posterior's row solve at the new points, then ONE workgroup forms S = K_new,new + diagonal - V V^T, factors it on chip and commits rows
+ * n .. n+k-1 of L, t = L^-1 y, the tile inverses and the LML only when every new pivot is positive.  Otherwise GP_ENOTPD, *info = the pivot in
+ * the numbering a fit of the extended data would report, and the model stays -- factor, cached matrices, LML, predictions, bit for bit -- at
+ * the size it had before the failing piece (earlier pieces of the same call stay appended).  For ARD-RBF models from gp_fit_rbf /
+ * gp_fit_rbf_dev; GP_EINVAL for a model from gp_fit_from_gram or gp_fit_co2, for one whose last (re)fit failed, for k < 1, ldx < k or a null
+ * pointer (the model is untouched).  Afterwards every entry point that takes the model works on the extended data; the cached matrices of the
+ * large-batch posterior and of the input gradients are updated in place (one block row each), never rebuilt.
+ * Both forms SYNCHRONISE once per piece -- the status read that atomicity needs; everything else of the _dev form is asynchronous on the
+ * context's stream.  Like gp_model_status they use the context's status word. */
+gp_status gp_model_append_dev(gp_model *model, const double *dX_new, int k, int ldx, const double *dy_new, int *info);
+gp_status gp_model_append    (gp_model *model, const double *X_new,  int k, int ldx, const double *y_new,  int *info);
 enum { GP_GET_L = 0, GP_GET_ALPHA = 1, GP_GET_LML = 2 };
 /* afterLearningComponents = (L, alpha, _) GpPredictor.scala:157; LML = GpPredictor.logLikelihood :144-149.
  * GP_GET_L: out is n x n with ld (zero strict upper); GP_GET_ALPHA: n doubles; GP_GET_LML: 1 double. */
