@@ -25,6 +25,7 @@ struct gp_small {
     double *dL = nullptr;       // G x (cap x cap), ld = cap, lower
     double *dLinv = nullptr;    // G x (cap x cap), ld = cap, lower
     double *dalpha = nullptr;   // G x cap
+    double *dalpha_next = nullptr;   // G x cap: gp_small_append builds the extended alpha here and swaps it in only if EVERY model succeeded
     double *dtheta = nullptr;   // G x (d + 2)
     bool has_y = false;
     std::vector<double> thetas;
@@ -145,6 +146,8 @@ __global__ __launch_bounds__(SM_THREADS) void small_trinv_kernel(int n, int cap,
 //   L^-1 <- [[L^-1, 0], [-(l^T L^-1) / lambda, 1 / lambda]]
 //   alpha = L^-T (L^-1 y) over the n + 1 points (targets in Y)
 // info[g] = n + 1 (1-based failing pivot, as breeze's cholesky would fail on the extended matrix) when lambda^2 <= 0.
+// Nothing inside the leading n x n parts of L and L^-1 is written, and `alpha` is a buffer of its own (never the batch's current
+// one): whether the append counts is decided by the host over ALL models, and until then every model still reads as before.
 __global__ __launch_bounds__(SM_THREADS) void small_append_kernel(int n, int cap, int d, double extra, const double *__restrict__ X,
                                                                   const double *__restrict__ Y, double *__restrict__ L, double *__restrict__ Linv,
                                                                   double *__restrict__ alpha, const double *__restrict__ theta, int *__restrict__ info) {
@@ -210,12 +213,14 @@ gp_status small_alloc(gp_ctx *ctx, int n, int d, int G, int capacity, gp_small *
     if (e == hipSuccess) e = hipMalloc(&s->dL, sizeof(double) * cc * G);
     if (e == hipSuccess) e = hipMalloc(&s->dLinv, sizeof(double) * cc * G);
     if (e == hipSuccess) e = hipMalloc(&s->dalpha, sizeof(double) * cap * G);
+    if (e == hipSuccess) e = hipMalloc(&s->dalpha_next, sizeof(double) * cap * G);
     if (e == hipSuccess) e = hipMalloc(&s->dtheta, sizeof(double) * (size_t)(d + 2) * G);
     if (e == hipSuccess) e = hipMemsetAsync(s->dX, 0, sizeof(double) * cap * d, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->dY, 0, sizeof(double) * cap * G, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->dL, 0, sizeof(double) * cc * G, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->dLinv, 0, sizeof(double) * cc * G, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->dalpha, 0, sizeof(double) * cap * G, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dalpha_next, 0, sizeof(double) * cap * G, ctx->stream);
     if (e != hipSuccess) {
         GP_SET_ERR(ctx, "small-model allocation (n=%d, capacity=%d, G=%d) failed: %s", n, s->cap, G, hipGetErrorString(e));
         gp_small_destroy(s);
@@ -411,7 +416,7 @@ gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
 void gp_small_destroy(gp_small *s) {
     if (!s) return;
     if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
-    void *ptrs[] = {s->dX, s->dY, s->dL, s->dLinv, s->dalpha, s->dtheta};
+    void *ptrs[] = {s->dX, s->dY, s->dL, s->dLinv, s->dalpha, s->dalpha_next, s->dtheta};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete s;
 }
@@ -490,7 +495,7 @@ gp_status gp_small_append(gp_small *s, const double *x_new, const double *y_new,
     dinfo = reinterpret_cast<int *>(dscr);
     GP_HIP(ctx, hipMemsetAsync(dinfo, 0, sizeof(int) * s->G, ctx->stream));
     hipLaunchKernelGGL(small_append_kernel, dim3(s->G), dim3(SM_THREADS), small_lds(cap, 3), ctx->stream, n, cap, s->d,
-                       std::isnan(s->sigma_noise) ? 0.0 : s->sigma_noise, s->dX, s->dY, s->dL, s->dLinv, s->dalpha, s->dtheta, dinfo);
+                       std::isnan(s->sigma_noise) ? 0.0 : s->sigma_noise, s->dX, s->dY, s->dL, s->dLinv, s->dalpha_next, s->dtheta, dinfo);
     GP_LAUNCH_CHECK(ctx);
     GP_HIP(ctx, hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * s->G, hipMemcpyDeviceToHost, ctx->stream));
     GP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -498,8 +503,11 @@ gp_status gp_small_append(gp_small *s, const double *x_new, const double *y_new,
         if (hinfo[g]) {
             if (info) *info = hinfo[g];
             GP_SET_ERR(ctx, "model %d: the extended matrix is not positive definite at pivot %d", g, hinfo[g]);
-            return GP_ENOTPD;   // nothing was committed for any model: n is unchanged
+            // n is unchanged and so is what every model reads: the models that succeeded wrote row n of L and L^-1, outside the
+            // n x n parts in use and overwritten by the next append, and their extended alpha only into dalpha_next
+            return GP_ENOTPD;
         }
+    std::swap(s->dalpha, s->dalpha_next);   // every model succeeded: the extended alphas become current
     s->n = n + 1;
     return GP_OK;
 }
