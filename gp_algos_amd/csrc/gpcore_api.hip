@@ -527,16 +527,26 @@ void build_lw(gp_ctx *ctx, double *Lw, double *scratch, const double *L, int np,
     gpk_lw_transpose(s, Lw, np, scratch, np, np, 0);
 }
 
+// GPCORE_POSTERIOR_TRI (default on, 0 = the full product; read per call): the Lw steps leave out the products with the zero half of Lw's
+// diagonal blocks.  Those zeros are exact wherever Lw comes from -- build_lw (the solved identity block: rows above the diagonal see only
+// 0 - 0 * L and 0 * inverse), the single-block rebuild of an append (the same solve), a grown model's new block row [0 | I] -- and the
+// rows of Vt are finite, pad rows included (predict_core), so both settings give the same bits.
+bool posterior_tri() {
+    const char *e = getenv("GPCORE_POSTERIOR_TRI");
+    return !e || atoi(e) != 0;
+}
+
 void solve_rows_lower(gp_ctx *ctx, double *Vt, int mp, const double *L, int np, int ldl, const double *dinv, double *sumsq,
                       const double *tvec = nullptr, double *dots = nullptr, const double *Lw = nullptr) {
     hipStream_t s = ctx->stream;
     const int nblk = np / GP_NB;
     if (Lw && sumsq && (mp / GP_NB) >= rows_left_min()) {
+        const bool tri_tail = posterior_tri();
         for (int i = 0; i < nblk; ++i) {
             const int K = (i + 1) * GP_NB;
             gp_prof_begin(ctx, GP_PROF_GEMM);
             gpk_gemm_nt_rowred(s, mp, GP_NB, K, Vt, mp, Lw + (size_t)i * GP_NB, np, Vt + (size_t)i * GP_NB * mp, mp, sumsq,
-                               tvec ? tvec + (size_t)i * GP_NB : nullptr, dots);
+                               tvec ? tvec + (size_t)i * GP_NB : nullptr, dots, tri_tail);
             gp_prof_end(ctx, GP_PROF_GEMM, 2.0 * mp * GP_NB * (double)K);
         }
         return;

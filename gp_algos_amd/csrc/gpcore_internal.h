@@ -111,8 +111,10 @@ void gpk_gemm_nt(hipStream_t s, int M, int N, int K, double alpha, const double 
 void gpk_gemm_k128_sub(hipStream_t s, int M, int N, const double *A, int lda, const double *B, int ldb, double *C, int ldc, int lower, int K = 128);
 // C[M x 128] = A[M x K] * B[128 x K]^T with fused row reductions (sumsq[m] += sum_n C(m,n)^2, dots[m] += sum_n C(m,n) tvec[n]);
 // C may be the last 128 columns of A (in-place posterior step).
+// tri_tail: the last 128 columns of B are a lower-triangular block with EXACT zeros above its diagonal (B(n, K - 128 + k) == 0 for k > n: the
+// diagonal blocks of Lw); the products that meet only those zeros are left out, and for finite A the result is bit for bit the full product's.
 void gpk_gemm_nt_rowred(hipStream_t s, int M, int N, int K, const double *A, int lda, const double *B, int ldb, double *C, int ldc,
-                        double *sumsq, const double *tvec, double *dots);
+                        double *sumsq, const double *tvec, double *dots, bool tri_tail = false);
 // ARD-RBF Gram.  theta on host.  symmetric: Xb == Xa, noise on the diagonal, tiles bi >= bj only (mirrored if full).
 // far_flag: one int of device memory owned by the caller's context and used in stream order (gp_gram_flag(ctx)); nullptr = the per-pair
 // kernel without the scan

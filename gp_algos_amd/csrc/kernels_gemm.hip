@@ -68,7 +68,10 @@ struct gemm_rowred {
     double *dots = nullptr;
 };
 
-template <int LOWER, int HAS_BETA, int NW, int RR = 0>
+// TRI (the posterior step on the folded factor Lw, see gemm_fused_kernel): the last 128 columns of K multiply a lower-triangular
+// 128 x 128 block of B, B(n, k) == 0 for k > n; in those eight k-tiles a wave leaves out the 16-column accumulator tiles that lie
+// wholly left of the k-tile (only +-0 would be added to them).
+template <int LOWER, int HAS_BETA, int NW, int RR = 0, int TRI = 0>
 __global__ __launch_bounds__(NW * 64, NW / 2) void gemm_nt_f64_kernel(int M, int N, int K, double alpha, const double *__restrict__ A, int lda,
                                                            const double *__restrict__ B, int ldb, double beta,
                                                            double *__restrict__ C, int ldc, int ktri, gp_batch bt, gemm_rowred rr,
@@ -162,25 +165,61 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void gemm_nt_f64_kernel(int M, int
     __syncthreads();
 
     const int fr = lane & 15, fk = lane >> 4;
-    for (int kt = 0; kt < KT; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
-        const double *Ac = As + cur * TK * LDS_STRIDE + wm + fr;
-        const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
+    if constexpr (!TRI) {
+        for (int kt = 0; kt < KT; ++kt) {
+            const int cur = kt & 1;
+            if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
+            const double *Ac = As + cur * TK * LDS_STRIDE + wm + fr;
+            const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
 #pragma unroll
-        for (int ks = 0; ks < TK / 4; ++ks) {
-            double af[4], bf[NT];
+            for (int ks = 0; ks < TK / 4; ++ks) {
+                double af[4], bf[NT];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+                for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * LDS_STRIDE + t * 16];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+                for (int t = 0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
+                for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+                    for (int mt = 0; mt < 4; ++mt)
+                        acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+            }
+            __syncthreads();   // drains the DMA of tile kt+1 (vmcnt) and fences the reads of tile kt
         }
-        __syncthreads();   // drains the DMA of tile kt+1 (vmcnt) and fences the reads of tile kt
+    } else {
+        // the k-tile of the loop above on this wave's accumulator tiles nt >= NT0 only; staging and barrier are the same for every NT0
+        auto ktile = [&](int kt, auto nt0_t) {
+            constexpr int NT0 = decltype(nt0_t)::value;
+            const int cur = kt & 1;
+            if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
+            if constexpr (NT0 < NT) {
+                const double *Ac = As + cur * TK * LDS_STRIDE + wm + fr;
+                const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
+#pragma unroll
+                for (int ks = 0; ks < TK / 4; ++ks) {
+                    double af[4], bf[NT];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+#pragma unroll
+                    for (int t = NT0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+#pragma unroll
+                    for (int nt = NT0; nt < NT; ++nt)
+#pragma unroll
+                        for (int mt = 0; mt < 4; ++mt)
+                            acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        };
+        // tail k-tile j (of 8) holds B columns 16 j ..: accumulator tile nt of this wave (columns wn + 16 nt ..) meets only zeros when
+        // wn / 16 + nt < j.  The k order inside every accumulator is unchanged.  (The launcher passes K >= 128.)
+        static_assert(!TRI || NT == 2, "the tail is written for the 8-wave form");
+        const int ct0 = __builtin_amdgcn_readfirstlane(wn >> 4);   // wave-uniform: the choice below is a scalar branch
+        const int kfull = KT - TN / TK + ct0;   // the last k-tile that meets all of this wave's columns; one tile less per k-tile after it
+        int kt = 0;
+        for (; kt <= kfull; ++kt) ktile(kt, std::integral_constant<int, 0>{});
+        if (kt < KT) ktile(kt++, std::integral_constant<int, 1>{});
+        for (; kt < KT; ++kt) ktile(kt, std::integral_constant<int, 2>{});
     }
 
     // epilogue: acc[nt][mt][r] = D[n = wn + nt*16 + fk + 4r][m = wm + mt*16 + fr].
@@ -270,7 +309,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void gemm_nt_f64_kernel(int M, int
 constexpr int FM = 256, FSTRIDE = FM + 16;
 // LOWER: tiles (bi, bj) of 256 x 128 whose last row reaches the diagonal (256 bi + 255 >= 128 bj); elements above the diagonal
 // are computed and not stored.  Tile rows are enumerated bi ascending, bj ascending inside.
-template <int LOWER, int HAS_BETA, int RR, int WV = 16>
+// TRI: B's last 128 columns of K are a lower-triangular block (the diagonal block of Lw); see the tail of the k loop.
+template <int LOWER, int HAS_BETA, int RR, int WV = 16, int TRI = 0>
 __global__ __launch_bounds__(WV * 64, 1) void gemm_fused_kernel(int M, int N, int K, double alpha, const double *A, int lda, const double *B, int ldb,
                                                             double beta, double *C, int ldc, gp_batch bt, gemm_rowred rr) {
     extern __shared__ __attribute__((aligned(16))) double fsm[];
@@ -324,25 +364,65 @@ __global__ __launch_bounds__(WV * 64, 1) void gemm_fused_kernel(int M, int N, in
     const int KT = K / TK;
     if (KT > 0) stage(0, 0);
     __syncthreads();
-    for (int kt = 0; kt < KT; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
-        const double *Ac = As + cur * TK * FSTRIDE + wm + fr;
-        const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
+    if constexpr (!TRI) {
+        for (int kt = 0; kt < KT; ++kt) {
+            const int cur = kt & 1;
+            if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
+            const double *Ac = As + cur * TK * FSTRIDE + wm + fr;
+            const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
 #pragma unroll
-        for (int ks = 0; ks < TK / 4; ++ks) {
-            double af[4], bf[NT];
+            for (int ks = 0; ks < TK / 4; ++ks) {
+                double af[4], bf[NT];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * FSTRIDE + t * 16];
+                for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * FSTRIDE + t * 16];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+                for (int t = 0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
+                for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+                    for (int mt = 0; mt < 4; ++mt)
+                        acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+            }
+            __syncthreads();
         }
-        __syncthreads();
+    } else {
+        // the k-tile of the loop above on this wave's accumulator tiles nt >= NT0 only; staging and barrier are the same for every NT0
+        auto ktile = [&](int kt, auto nt0_t) {
+            constexpr int NT0 = decltype(nt0_t)::value;
+            const int cur = kt & 1;
+            if (kt + 1 < KT) stage(cur ^ 1, kt + 1);
+            if constexpr (NT0 < NT) {
+                const double *Ac = As + cur * TK * FSTRIDE + wm + fr;
+                const double *Bc = Bs + cur * TK * LDS_STRIDE + wn + fr;
+#pragma unroll
+                for (int ks = 0; ks < TK / 4; ++ks) {
+                    double af[4], bf[NT];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) af[t] = Ac[(ks * 4 + fk) * FSTRIDE + t * 16];
+#pragma unroll
+                    for (int t = NT0; t < NT; ++t) bf[t] = Bc[(ks * 4 + fk) * LDS_STRIDE + t * 16];
+#pragma unroll
+                    for (int nt = NT0; nt < NT; ++nt)
+#pragma unroll
+                        for (int mt = 0; mt < 4; ++mt)
+                            acc[nt][mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        };
+        // tail k-tile j (of 8) holds B columns 16 j ..: accumulator tile nt of this wave (columns wn + 16 nt ..) meets only zeros when
+        // wn / 16 + nt < j, so the wave issues tiles nt >= j - wn / 16 and reads only their B fragments.  Waves w and w + 4 share a SIMD
+        // and own columns 0-63 and 64-127: per SIMD the eight tail tiles cost 8, 7, ..., 1 units of 4 x 4 MFMAs, the same on all four.
+        // The k order inside every accumulator is unchanged.  (The launcher passes K >= 128.)
+        static_assert(!TRI || NT == 4, "the tail is written for the 8-wave form");
+        const int ct0 = __builtin_amdgcn_readfirstlane(wn >> 4);   // wave-uniform: the choice below is a scalar branch
+        const int kfull = KT - TN / TK + ct0;   // the last k-tile that meets all of this wave's columns; one tile less per k-tile after it
+        int kt = 0;
+        for (; kt <= kfull; ++kt) ktile(kt, std::integral_constant<int, 0>{});
+        if (kt < KT) ktile(kt++, std::integral_constant<int, 1>{});
+        if (kt < KT) ktile(kt++, std::integral_constant<int, 2>{});
+        if (kt < KT) ktile(kt++, std::integral_constant<int, 3>{});
+        for (; kt < KT; ++kt) ktile(kt, std::integral_constant<int, 4>{});
     }
     const bool diag = LOWER && (row0 < col0 + TN);   // the tile touches or crosses the diagonal
     double rsq[4] = {0.0, 0.0, 0.0, 0.0}, rdt[4] = {0.0, 0.0, 0.0, 0.0};
@@ -557,14 +637,18 @@ void gpk_gemm_nt(hipStream_t s, int M, int N, int K, double alpha, const double 
 
 // C = A B^T (no beta) with the row reductions above; C may alias the last N columns of A (each tile reads only its own
 // rows of A and stores after its k loop) -- the in-place posterior step.
+// tri_tail: the caller guarantees B(n, k) == 0 (exactly) for k > K - 128 + n, i.e. the last 128 columns of B are a lower-triangular
+// block; the kernels then leave out the products that meet only those zeros.  With finite A the result is bit for bit the full product's.
 // per device, from gp_ctx_create: the fused kernel's 106 KB of LDS is above the default dynamic limit
 int gpk_init_gemm_kernels() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_fused_kernel<0, 0, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess ? 0 : 1;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_fused_kernel<0, 0, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) != hipSuccess) return 1;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_fused_kernel<0, 0, 1, 8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess ? 0 : 1;
 }
 
 void gpk_gemm_nt_rowred(hipStream_t s, int M, int N, int K, const double *A, int lda, const double *B, int ldb, double *C, int ldc,
-                        double *sumsq, const double *tvec, double *dots) {
+                        double *sumsq, const double *tvec, double *dots, bool tri_tail) {
     if (M <= 0 || N != TN) return;   // one column tile: a tile is the only writer of its rows' accumulators
+    if (K < TN) tri_tail = false;    // no whole triangular block to speak of
     // 256-row tiles by ONE 8-wave workgroup per CU where they fit (8 waves x 64x64; 16 waves x 64x32 measured 0.6 % slower: a third more
     // LDS fragment reads in a power-limited loop); an odd 128-row remainder goes through the 128-row kernel below
     if (M >= FM) {
@@ -580,7 +664,8 @@ void gpk_gemm_nt_rowred(hipStream_t s, int M, int N, int K, const double *A, int
         if (Mf == 0) goto small_tiles;
         gemm_rowred r2;
         r2.sumsq = sumsq, r2.tvec = tvec, r2.dots = dots;
-        hipLaunchKernelGGL((gemm_fused_kernel<0, 0, 1, 8>), dim3(Mf / FM), dim3(512), FUSED_LDS, s, Mf, TN, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, gp_batch(), r2);
+        if (tri_tail) hipLaunchKernelGGL((gemm_fused_kernel<0, 0, 1, 8, 1>), dim3(Mf / FM), dim3(512), FUSED_LDS, s, Mf, TN, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, gp_batch(), r2);
+        else hipLaunchKernelGGL((gemm_fused_kernel<0, 0, 1, 8>), dim3(Mf / FM), dim3(512), FUSED_LDS, s, Mf, TN, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, gp_batch(), r2);
         if (Mf == M) return;
         A += Mf, C += Mf, sumsq += Mf, M -= Mf;
         if (dots) dots += Mf;
@@ -589,7 +674,8 @@ small_tiles:
     gemm_rowred rr;
     rr.sumsq = sumsq, rr.tvec = tvec, rr.dots = dots;
     const int ntiles = (M / TM) * (N / TN);
-    hipLaunchKernelGGL((gemm_nt_f64_kernel<0, 0, 8, 1>), dim3(ntiles), dim3(512), 0, s, M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, 0, gp_batch(), rr, nullptr, 0, nullptr);
+    if (tri_tail) hipLaunchKernelGGL((gemm_nt_f64_kernel<0, 0, 8, 1, 1>), dim3(ntiles), dim3(512), 0, s, M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, 0, gp_batch(), rr, nullptr, 0, nullptr);
+    else hipLaunchKernelGGL((gemm_nt_f64_kernel<0, 0, 8, 1>), dim3(ntiles), dim3(512), 0, s, M, N, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, 0, gp_batch(), rr, nullptr, 0, nullptr);
 }
 
 // C (M x N, lower trapezoid if `lower`) -= A (M x 128) B (N x 128)^T; M, N multiples of 64
