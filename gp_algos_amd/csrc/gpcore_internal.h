@@ -42,7 +42,8 @@ struct gp_ctx {
     int prof_which = GP_PROF_OFF;
     gp_prof_slot prof[GP_PROF_NCLASSES];
     int num_cu = 256;
-    int lookahead = -1;           // far trailing update of the Cholesky on the side stream: 1 on, 0 off, -1 by size (chol_blocked); GPCORE_LOOKAHEAD
+    int lookahead = -1;           // far trailing update of the Cholesky on the side stream: 1 on, 0 off, -1 by size (gpi_chol_blocked); GPCORE_LOOKAHEAD
+    struct gp_chol_mega *mega = nullptr;   // the single-launch Cholesky's state, owned by gpcore_chol.hip: made on first use, freed by gpi_chol_mega_free
     char err[512] = {0};
     // scratch reused across calls
     double *d_scalars = nullptr;  // small device scratch (256 doubles)
@@ -218,7 +219,14 @@ gp_status gpi_ucb_lbfgs_lockstep(int d, const double *starts, int c, int lds, in
                                  const std::function<gp_status(const double *, int, double *, double *)> &evaluate,
                                  double *best_x, double *best_val, int *evals_out);
 gp_status gpi_ctx_ep_streams(gp_ctx *ctx);   // side2 / side3, created on first use
-void gpi_chol_blocked(gp_ctx *ctx, double *A, int np, int lda, double *dinv, int extra);
+
+// ---- factorisation and triangular drivers (defined in gpcore_chol.hip) ----
+void gpi_chol_mega_free(gp_ctx *ctx);        // the single-launch state of a context that is being destroyed
+int *gpi_chol_mega_err(gp_ctx *ctx);         // device address of the single launch's error word, nullptr while the context has none (gpi_read_info)
+double gpi_syrk_flops(int r, int K);         // flops of the lower-trapezoid tiles of an r x r product with inner dimension K
+// the two-level blocked factorisation; count > 1: a lockstep batch (problem g at A + g*strideA, dinv + g*strideDinv, info + g)
+void gpi_chol_blocked(gp_ctx *ctx, double *A, int np, int lda, double *dinv, int extra, int count = 1, size_t strideA = 0, size_t strideDinv = 0,
+                      int *info = nullptr);
 // one 128-column step (diagonal block k0) of the same two-level factorisation on stream s, for callers that feed the columns
 // one block at a time: diagonal factor, panel solve, in-panel update, and the K = OUTER trailing update when k0 closes an outer panel
 void gpi_chol_panel_step(gp_ctx *ctx, hipStream_t s, double *A, int np, int lda, double *dinv, int extra, int k0, hipEvent_t solved = nullptr,
@@ -226,10 +234,13 @@ void gpi_chol_panel_step(gp_ctx *ctx, hipStream_t s, double *A, int np, int lda,
                          int count = 1, size_t strideA = 0, size_t strideDinv = 0, int *info = nullptr);   // count > 1: a lockstep batch (info + g per problem)
 void gpi_solve_rows_lower(gp_ctx *ctx, double *Vt, int mp, const double *L, int np, int ldl, const double *dinv, double *sumsq,
                           const double *tvec = nullptr, double *dots = nullptr, const double *Lw = nullptr);   // Lw: see gpi_build_lw
-// the folded factor of the left-looking posterior batches (gpcore_api.hip build_lw): Lw and scratch np x np; gpi_solve_rows_lower takes it
+// the folded factor of the left-looking posterior batches: Lw and scratch np x np; gpi_solve_rows_lower takes it
 // from gpi_rows_left_min() row tiles on (GPCORE_ROWS_LEFT_MIN, read per call)
 void gpi_build_lw(gp_ctx *ctx, double *Lw, double *scratch, const double *L, int np, int ldl, const double *dinv);
 int gpi_rows_left_min();
+void gpi_solve_rows_upper(gp_ctx *ctx, double *Vt, int mp, const double *U, int np, int ldu);
 void gpi_back_solve_vec(gp_ctx *ctx, const double *L, int np, int ldl, const double *dinv, double *z, double *alpha);
-void gpi_inverse_transpose_lower(gp_ctx *ctx, double *T, const double *L, int np, int ldl, const double *dinv);
+void gpi_inverse_transpose_lower(gp_ctx *ctx, double *T, const double *L, int np, int ldl, const double *dinv, int count = 1, size_t strideT = 0,
+                                 size_t strideL = 0, size_t strideDinv = 0, bool lower_is_zero = false);
+gp_status gpi_trsm_impl(gp_ctx *ctx, int trans, const double *L, int n, int ldl, double *B, int nrhs, int ldb);   // the body of gp_trsm_lower
 void gpi_forward_solve_vec(gp_ctx *ctx, const double *L, int np, int ldl, const double *dinv, double *t, double *z);
