@@ -1551,5 +1551,5 @@ extern "C" gp_status gp_optimize_rbf(gp_ctx *ctx, const double *X, int n, int d,
 }
 
 // ------------------------------------------------------------------------------------------------
-// EP classification -- implemented in gpcore_ep.hip
+// EP classification -- implemented in gpcore_ep.hip and gpcore_ep_eval.hip
 // ------------------------------------------------------------------------------------------------

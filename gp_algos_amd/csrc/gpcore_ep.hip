@@ -12,67 +12,15 @@
 // so a sweep costs 2 n^3 MFMA flops and 16 n^3 / 128 bytes instead of 24 n^3 bytes.  The end-of-sweep
 // refactorisation (L = chol(I + S^1/2 K S^1/2), V = L \ S^1/2 K, Sigma = K - V^T V, mu = Sigma nu) reuses
 // the blocked Cholesky, the row-panel solve and the MFMA syrk of the regression path.
-#include "gpcore_internal.h"
+// This file: the state, the site-loop and refactorisation kernels and the sweep (one driver for a single run and for a lockstep batch);
+// what is computed FROM a fitted state (LML, gradient, prediction, grid of settings, optimiser) is gpcore_ep_eval.hip.
+#include "ep_state.h"
 #include "dpp_tile.h"
 #include "trsm_tile.h"
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <new>
-#include <thread>
-#include <vector>
-
-// Outer panel of the site loop's delayed updates (two-level, like the Cholesky): the columns up to one block past the current outer
-// panel take every block's rank-128 update at once (the chain needs them), everything to the right ONE rank-EP_OUTER update per panel.
-constexpr int EP_OUTER = 4 * GP_NB;
-
-struct gp_ep {
-    gp_ctx *ctx = nullptr;
-    int n = 0, np = 0;
-    double *K = nullptr;      // np x np, full symmetric, pad = identity
-    double *Sig = nullptr;    // np x np, full symmetric
-    double *Sig2 = nullptr;   // np x np: the NEXT Sigma, built under the site loop by the streamed refactorisation (allocated on first use)
-    double *L = nullptr;      // (2 np) x np, ld = ldl = 2 np: rows [0, np) the lower factor of B = I + S^1/2 K S^1/2, rows [np, 2 np) ride through
-                              //   the factorisation and come out as Vt = (K S^1/2) L^-T  (V = L \ (S^1/2 K), :59)
-    int ldl = 0;
-    double *dinv = nullptr;   // np x 16
-    double *S = nullptr;      // np x 128 panel of delayed columns
-    double *Sc = nullptr;     // np x EP_OUTER: the delayed columns scaled by c, one 128-column block per site block of the current outer panel
-    double *blk = nullptr;    // 2 x (128 x 128 unit-lower block factor + its 8 tile inverses), by block parity
-    double *vec = nullptr;    // 10 x np: tau, nu, tau_old, nu_old, mu, cav_tau, cav_nu, st, tmp1, tmp2
-    double *cvec = nullptr;   // 2 x (128 c + 128 coef), by block parity
-    std::vector<hipEvent_t> ev;   // 4 per block: block factor ready | next block's rows solved | side-stream update done | Vt block column final
-    hipEvent_t ev_chol = nullptr, ev_parta = nullptr, ev_partb = nullptr;   // end-of-sweep refactorisation: see ep_refactor
-    hipEvent_t ev_w = nullptr, ev_pipe = nullptr;   // streamed refactorisation: sweep start on the main stream | its last launch
-    int *flags = nullptr;         // np/128 device flags (+ 1 error word): "solved rows of block b are in memory" (ep_block2_kernel -> side stream)
-    int epoch = 0;                // token of the current sweep's flags; never reset, so a stale flag cannot match
-    int *uflags = nullptr;        // np/128 counters: urgent tiles of block b's trailing update stored (two per sweep; gpk_gemm_nt -> ep_block2_kernel)
-    int uepoch = 0;               // sweeps that counted so far: block b's counter stands at 2 * uepoch when its tiles of this sweep are in
-    bool owns = true;             // false: a view into an ep_slab (problem g of a lockstep batch); the slab's first problem owns the memory
-    bool side_pending = false;    // the side stream still owes the second part of Sigma / mu
-    bool sig_mirrored = false;    // the strict upper triangle of Sig mirrors the lower one (only gp_ep_get needs it)
-    int *y = nullptr;
-    int sweeps = 0;
-    // gp_ep_create_rbf only: the training inputs and the kernel K was built from (gp_ep_predict_rbf rebuilds K* with them)
-    int d = 0;
-    double *dX = nullptr;       // n x d, ld = n
-    double *dcen = nullptr;     // d: centroid of the rows of dX (centre of the matrix-core Gram forms)
-    std::vector<double> theta;  // d + 2
-    double *Lw = nullptr;       // np x np folded factor of large classify batches (gpi_build_lw), allocated on first use
-    bool lw_valid = false;      // Lw belongs to the L now in place: cleared wherever L changes
-    double *tau() { return vec; }
-    double *nu() { return vec + np; }
-    double *tau_old() { return vec + 2 * (size_t)np; }
-    double *nu_old() { return vec + 3 * (size_t)np; }
-    double *mu() { return vec + 4 * (size_t)np; }
-    double *cav_tau() { return vec + 5 * (size_t)np; }
-    double *cav_nu() { return vec + 6 * (size_t)np; }
-    double *st() { return vec + 7 * (size_t)np; }
-    double *tmp1() { return vec + 8 * (size_t)np; }
-    double *tmp2() { return vec + 9 * (size_t)np; }
-};
 
 namespace {
 
@@ -92,7 +40,6 @@ __device__ __forceinline__ double rl64(double v, int lane) {
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double dnorm_d(double x) { return exp(-(x * x) / 2.0 - log(sqrt(2.0 * M_PI))); }   // StatsUtils.scala:15
-__device__ __forceinline__ double pnorm_d(double x) { return 0.5 * (1.0 + erf(x / sqrt(2.0))); }              // StatsUtils.scala:17
 
 // A(I-tile, J-tile) -= (S(I-tile, chunk) diag(c)) S(J-tile, chunk)^T for the 16 columns of the chunk starting at column cs0: one
 // 16 x 16 tile of the block's delayed update on the matrix cores, operands and result in LDS (leading dimension LS)
@@ -363,7 +310,6 @@ struct ep_strides {
 };
 constexpr int EP2_XS = 144;   // LDS column stride of the prologue's 128-row strip: 1152 B = 128 (mod 256) -> conflict-free fragments
 constexpr int EP_BLOCK2_LDS = (GP_NB * EP2_XS + 8 * GP_NB + 5 * GP_NB + 16) * (int)sizeof(double);   // 160 896 B of the CU's 163 840
-constexpr int EP_BLK_ELEMS = GP_NB * GP_NB + 8 * 256;   // Lmat + its tile inverses
 
 // Everything of chunk j (sites 16 j .. 16 j + 15) that other kernels read, written by the three helper waves while wave 0 runs
 // the next chunk: the chunk's columns of the unit-lower factor Lmat = I + strict_lower(S diag(c)) (final as soon as its sites are:
@@ -806,123 +752,12 @@ __global__ void vec_sqrt_kernel(double *__restrict__ out, const double *__restri
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < np) out[i] = (i < n) ? sqrt(in[i]) : 0.0;
 }
-__global__ void vec_div_kernel(double *__restrict__ out, const double *__restrict__ a, const double *__restrict__ b, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = a[i] / b[i];
-}
-__global__ void vec_sub_kernel(double *__restrict__ out, const double *__restrict__ a, const double *__restrict__ b, int n, int np) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < np) out[i] = (i < n) ? a[i] - b[i] : 0.0;
-}
-// M(i,j) = st_i * M(i,j) * st_j on the lower triangle
-__global__ void scale_sym_lower_kernel(double *__restrict__ M, const double *__restrict__ st, int n, int ld) {
-    for (int j = blockIdx.y; j < n; j += gridDim.y)
-        for (int i = j + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) M[i + (size_t)j * ld] *= st[i] * st[j];
-}
-__global__ void vec_mul_kernel(double *__restrict__ out, const double *__restrict__ a, const double *__restrict__ b, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = a[i] * b[i];
-}
-// w = nu - st o z
-__global__ void ep_w_kernel(double *__restrict__ w, const double *__restrict__ nu, const double *__restrict__ st, const double *__restrict__ z, int n, int np) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < np) w[i] = (i < n) ? nu[i] - st[i] * z[i] : 0.0;
-}
-__global__ void ep_prob_kernel(double *__restrict__ prob, const double *__restrict__ fmean, const double *__restrict__ sumsq,
-                               const double *__restrict__ kss, int m) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) prob[i] = pnorm_d(fmean[i] / sqrt(1.0 + (kss[i] - sumsq[i])));   // GpClassifier.scala:43-45
-}
-// the same for the kernel's constant test diagonal kss = sf^2 + sn^2; also hands out the latent mean (:37) and variance (diagonal of :41)
-__global__ void ep_prob_latent_kernel(double *__restrict__ prob, double *__restrict__ fmean_out, double *__restrict__ fvar_out,
-                                      const double *__restrict__ fmean, const double *__restrict__ sumsq, double kss, int m) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double fm = fmean[i], fv = kss - sumsq[i];
-    prob[i] = pnorm_d(fm / sqrt(1.0 + fv));
-    if (fmean_out) fmean_out[i] = fm;
-    if (fvar_out) fvar_out[i] = fv;
-}
-
-// One pass over a batch of the test-train block Vt (mp x np, column-major, ld mp; rows < m and columns < n hold K*) in front of the
-// row solve of GpClassifier.scala:38-41:
-//   fmean[r] = sum_{j<n} K*[r,j] w[j]  (:37),   K*[r,j] <- K*[r,j] st[j]  (:38),   exact zeros in columns n..np-1 and rows m..mp-1
-// (the pad of Vt holds whatever the last user of the workspace left, and nothing guarantees the pad entries of st: both are
-// never read).  A workgroup owns 128 rows: lane l of every wave rows 2l, 2l+1 (16 bytes per lane, a wave reads and writes 1 KiB of a
-// column at a time); wave c owns column chunk c of EP_MS_CHUNKS, so w[j] and st[j] are wave-uniform loads.  The chunk partials meet in
-// LDS and are added in chunk order: no atomics, the same bits on every run.
-constexpr int EP_MS_CHUNKS = 8;
-__global__ __launch_bounds__(64 * EP_MS_CHUNKS) void ep_mean_scale_kernel(double *__restrict__ Vt, int mp, int np, int m, int n,
-                                                                          const double *__restrict__ w, const double *__restrict__ st,
-                                                                          double *__restrict__ fmean) {
-    __shared__ double part[EP_MS_CHUNKS][GP_NB];
-    const int lane = threadIdx.x & 63;
-    const int ch = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int r0 = blockIdx.x * GP_NB + 2 * lane;          // < mp: the grid is mp / 128 workgroups
-    const bool live0 = r0 < m, live1 = r0 + 1 < m;
-    const int cw = np / EP_MS_CHUNKS;                      // np is a multiple of 128
-    const int j0 = ch * cw, j1 = j0 + cw;
-    const int jn = n < j0 ? j0 : (n < j1 ? n : j1);        // [j0, jn): columns of K*, [jn, j1): pad
-    double2 *col = reinterpret_cast<double2 *>(Vt + r0 + (size_t)j0 * mp);     // r0 and mp are even: 16-byte aligned
-    const size_t stride = (size_t)mp / 2;
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll 8
-    for (int j = j0; j < jn; ++j, col += stride) {
-        const double wj = w[j], sj = st[j];
-        double2 v = *col;
-        v.x = live0 ? v.x : 0.0;
-        v.y = live1 ? v.y : 0.0;
-        a0 = fma(v.x, wj, a0);
-        a1 = fma(v.y, wj, a1);
-        v.x *= sj;
-        v.y *= sj;
-        *col = v;
-    }
-    for (int j = jn; j < j1; ++j, col += stride) *col = make_double2(0.0, 0.0);
-    part[ch][2 * lane] = a0;
-    part[ch][2 * lane + 1] = a1;
-    __syncthreads();
-    if (threadIdx.x < GP_NB) {
-        double acc = part[0][threadIdx.x];
-#pragma unroll
-        for (int c = 1; c < EP_MS_CHUNKS; ++c) acc += part[c][threadIdx.x];
-        fmean[blockIdx.x * GP_NB + threadIdx.x] = acc;
-    }
-}
-
-// EP log marginal likelihood (EpParameterEstimator.scala:71-96); strict: the fourth/first term is dropped as compiled
-__global__ __launch_bounds__(1024) void ep_lml_kernel(int n, int ldl, const double *__restrict__ L, const double *__restrict__ tau,
-                                                      const double *__restrict__ nu, const double *__restrict__ mu,
-                                                      const double *__restrict__ cav_tau, const double *__restrict__ cav_nu,
-                                                      const int *__restrict__ y, int strict, double *__restrict__ out) {
-    __shared__ double red[1024];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) {
-        const double ct = cav_tau[i], cm = cav_nu[i] / ct, T = tau[i] + ct;
-        double third = log(pnorm_d(y[i] * cm / sqrt(1.0 + 1.0 / ct)));
-        double fourth = strict ? 0.0 : 0.5 * log(1.0 + tau[i] / ct) - log(L[i + (size_t)i * ldl]);
-        // 0.5 * [ nu^T (Sigma - diag(1/T)) nu + sum (cm ct / T)(tau cm - 2 nu) ],  nu^T Sigma nu = nu . mu
-        double first = nu[i] * mu[i] - nu[i] * nu[i] / T;
-        double second = ((cm * ct) * (1.0 / T)) * (tau[i] * cm - nu[i] * 2.0);
-        acc += third + fourth + 0.5 * (first + second);
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
-
-inline dim3 g1(int n) { return dim3((n + 255) / 256); }
 
 // out[i] = sum_j A(i,j) x[j] for rows i in [lo, lo + m) of a SYMMETRIC n x n matrix of which only the lower triangle is stored
 // (mu = Sigma nu, EpParameterEstimator.scala:61, without mirroring Sigma first), in three small launches with a fixed
 // summation order:  row part  sum_{j <= i} A(i,j) x[j]  (thread = row, coalesced over i, the j range cut into SYMV_CHUNKS
 // chunks -> partial[chunk][i]);  column part  sum_{j > i} A(j,i) x[j]  (one wave per column, lanes striding the rows ->
 // partial[SYMV_CHUNKS][i]);  then the chunks are added in order.
-constexpr int SYMV_CHUNKS = 16;
 __global__ __launch_bounds__(256) void ep_symv_rows_kernel(const double *__restrict__ A, int ld, int n, const double *__restrict__ x,
                                                            double *__restrict__ partial, int lo, int m, size_t sA = 0, size_t sx = 0, size_t sp = 0) {
     A += (size_t)blockIdx.z * sA, x += (size_t)blockIdx.z * sx, partial += (size_t)blockIdx.z * sp;   // blockIdx.z = problem
@@ -970,6 +805,12 @@ void ep_symv_lower(hipStream_t s, const double *A, int ld, int n, const double *
     hipLaunchKernelGGL(ep_symv_sum_kernel, dim3((m + 255) / 256, 1, count), dim3(256), 0, s, partial, n, out, lo, m, sp, sx);
 }
 
+}  // namespace
+
+void ep_scale_cols(hipStream_t s, int blocks, double *dst, int ldd, const double *src, int lds, const double *c, int rows, int cols) {
+    hipLaunchKernelGGL(scale_cols_kernel, dim3(blocks), dim3(256), 0, s, dst, ldd, src, lds, c, rows, cols);
+}
+
 // end of sweep: L, Sigma, mu from the current site parameters (EpParameterEstimator.scala:56-61)
 //   B = I + S^1/2 K S^1/2 in rows [0, np) of ep->L, K S^1/2 in rows [np, 2 np): ONE blocked factorisation leaves L on top and
 //   Vt = (K S^1/2) L^-T below it (the extra rows ride through the panel solves and the trailing updates exactly like y^T does
@@ -979,7 +820,7 @@ void ep_symv_lower(hipStream_t s, const double *A, int ld, int n, const double *
 //   stream, the other (np/128 - 4)(np/128 - 3)/2 tiles -- one resident round at n = 4096 instead of 528 tiles = one round
 //   plus a 16-tile tail -- on the side stream, under the next sweep's first block kernels.  The side stream's work of the next
 //   sweep is queued behind it, and the main stream only reads beyond column 512 after it has waited for that work.
-gp_status ep_refactor(gp_ep *ep) {
+static gp_status ep_refactor(gp_ep *ep) {
     gp_ctx *ctx = ep->ctx;
     hipStream_t s = ctx->stream, s2 = ctx->side;
     const int n = ep->n, np = ep->np, ldl = ep->ldl;
@@ -1023,7 +864,7 @@ gp_status ep_refactor(gp_ep *ep) {
 }
 
 // everything the side stream still owes (second part of Sigma and mu) is ordered before whatever the main stream does next
-gp_status ep_join_side(gp_ep *ep) {
+static gp_status ep_join_side(gp_ep *ep) {
     if (ep->side_pending) GP_HIP(ep->ctx, hipStreamWaitEvent(ep->ctx->stream, ep->ev_partb, 0));
     ep->side_pending = false;
     return GP_OK;
@@ -1031,7 +872,7 @@ gp_status ep_join_side(gp_ep *ep) {
 
 // device buffers + labels; K is left for the caller to fill (host upload or device Gram), then ep_start()
 // G > 1: every buffer holds G problems back to back (ep_slab); the returned object is problem 0 and owns the memory
-gp_status ep_alloc(gp_ctx *ctx, int n, const int32_t *y, gp_ep **out, int G = 1) {
+gp_status ep_alloc(gp_ctx *ctx, int n, const int32_t *y, gp_ep **out, int G) {
     *out = nullptr;
     for (int i = 0; i < n; ++i) GP_REQUIRE(ctx, y[i] == 1 || y[i] == -1, "targets must contain values from set {-1,1}");
     GP_HIP(ctx, hipSetDevice(ctx->device));
@@ -1096,7 +937,7 @@ gp_status ep_start(gp_ep *ep) {
 // (A two-level form -- rank-128 updates on the columns the chain reads next, one rank-512 update per outer panel for the rest -- was
 // measured equal in a batch, 228.9 vs 229.1 sweeps/s aggregate, and slower in a single run, 184.7 vs 188.0: the site loop's updates are
 // an eighth of a sweep's flops.  Removed in round 4.)
-void ep_trailing_update(gp_ctx *ctx, hipStream_t st, int np, int i0, double *Sc, double *Sig, gp_batch bt, int *uflag = nullptr) {
+static void ep_trailing_update(gp_ctx *ctx, hipStream_t st, int np, int i0, double *Sc, double *Sig, gp_batch bt, int *uflag = nullptr) {
     const int pb = i0 / GP_NB - 1, jb = pb % (EP_OUTER / GP_NB);
     const int M = np - i0;
     if (M <= GP_NB) return;          // block b is the last one: nothing below or right of it
@@ -1106,30 +947,6 @@ void ep_trailing_update(gp_ctx *ctx, hipStream_t st, int np, int i0, double *Sc,
                 Sig + (size_t)i0 + (size_t)i0 * np, np, 1, 0, bt, nullptr, 0, uflag);
     gp_prof_end(ctx, GP_PROF_GEMM, bt.count * tiles * 2.0 * GP_NB * GP_NB * GP_NB, st);
 }
-
-// ---- lockstep batch: G EP problems of one size advance through a sweep together (MeshHyperParamsLogLikelihoodEvaluator.scala:26-40
-// and the trial steps of HyperParamsOptimization.scala:31-55 evaluate independent settings one after the other) ----
-// A single sweep is bound by its serial site chain (one workgroup per block of 128 sites) and by the launch latencies of the ~12
-// small kernels per block that feed it; the matrix work beside it leaves most of the chip idle (C4: 33 of 78 TFLOP/s).  G problems
-// share every launch instead: the chain kernel runs as G workgroups on G CUs (blockIdx.x = problem), the solves, updates and the
-// refactorisation under the site loop as gp_batch launches with G times the tiles -- the same sweep, the same arithmetic per problem
-// (bit for bit: every kernel computes a problem's tiles exactly as in a single run), G times the work per launch latency.
-struct ep_slab {
-    gp_ctx *ctx = nullptr;
-    int n = 0, np = 0, G = 0;
-    std::vector<gp_ep *> ep;        // ep[0] owns the memory, ep[g] views problem g
-    int *info = nullptr;            // G failing-pivot words
-    double *partial = nullptr;      // G x (SYMV_CHUNKS + 1) x np
-    size_t sMat() const { return (size_t)np * np; }
-    size_t sL() const { return (size_t)2 * np * np; }
-    size_t sVec() const { return (size_t)10 * np; }
-    size_t sBlk() const { return (size_t)2 * EP_BLK_ELEMS; }
-    size_t sCv() const { return (size_t)4 * GP_NB; }
-    size_t sSc() const { return (size_t)np * EP_OUTER; }
-    size_t sDinv() const { return (size_t)np * 16; }
-    int sFlag() const { return np / GP_NB + 1; }
-    size_t sPart() const { return (size_t)(SYMV_CHUNKS + 1) * np; }
-};
 
 void ep_slab_free(ep_slab &sl) {
     if (sl.ctx) (void)hipSetDevice(sl.ctx->device);
@@ -1167,103 +984,221 @@ gp_status ep_slab_alloc(gp_ctx *ctx, int n, const int32_t *y, int G, ep_slab &sl
     return GP_OK;
 }
 
-// ONE sweep of problems 0 .. count-1 of the slab: gp_ep_sweep's fused chain + streamed refactorisation, every launch a batch.
-gp_status ep_sweep_lockstep(ep_slab &sl, int count) {
+// The form of a sweep: which variants of the chain and of the refactorisation run, on how many problems, and where those lie.  The
+// callers read the knobs (gp_ep_sweep for a single run, ep_slab_sweep for a lockstep batch: their defaults differ); ep_sweep_once
+// only enqueues.
+struct ep_sweep_form {
+    int count = 1;                // problems in every launch: problem g lies g strides behind problem 0's buffers
+    size_t sMat = 0, sL = 0, sVec = 0, sBlk = 0, sCv = 0, sSc = 0, sDinv = 0, sPart = 0;   // ep_slab's strides; a single run leaves them zero
+    int sFlag = 0;                //   (every kernel takes its path by the count, never by the strides)
+    int *info = nullptr;          // count failing-pivot words
+    double *partial = nullptr;    // count x (SYMV_CHUNKS + 1) x np, streamed refactorisation only
+    bool overlap = true, pipe = false, fused = false, fused_link = false, urgent = false;
+    bool far_split = false;       // the far part of the factorisation's trailing updates goes to s4
+    int sig_blocks = 2;           // site blocks per next-covariance update
+    hipStream_t s4 = nullptr;     // stream of the next-covariance updates
+    int *uerr = nullptr;          // error word of the chain kernel's wait for the urgent tiles
+};
+
+// ONE sweep of problems 0 .. f.count-1 of eps (a single run: one problem; a lockstep batch: the views of a slab, every launch a batch).
+// Only the fused chain under the streamed refactorisation has kernels that take per-problem strides.
+static gp_status ep_sweep_once(gp_ep *const *eps, int nep, const ep_sweep_form &f) {
+    gp_ep *ep = eps[0];
+    gp_ctx *ctx = ep->ctx;
+    const int count = f.count;
+    const bool overlap = f.overlap, pipe = f.pipe, fused = f.fused, urgent = f.urgent;
+    GP_REQUIRE(ctx, count >= 1 && count <= nep, "EP sweep: problem count outside the slab");
+    GP_REQUIRE(ctx, count == 1 || (fused && pipe), "EP sweep: only the fused chain under the streamed refactorisation runs as a batch");
+    hipStream_t s = ctx->stream, s2 = ctx->side, s3 = ctx->side2, s4 = f.s4;
+    const int n = ep->n, np = ep->np, nblk = np / GP_NB, ldl = ep->ldl;
+    for (int g = 0; g < count; ++g) eps[g]->lw_valid = false;     // every problem's L is rewritten (both refactorisation forms)
+    ep_strides es;
+    es.sig = f.sMat, es.vec = f.sVec, es.y = 0, es.blk = f.sBlk, es.cvec = f.sCv, es.sc = f.sSc, es.flag = f.sFlag;
+    gp_batch bSig, bTrsm, bVt;
+    bSig.count = bTrsm.count = bVt.count = count;
+    bSig.s0 = f.sSc, bSig.s1 = f.sMat, bSig.s2 = f.sMat;                      // C (Sigma) -= A (Sc) B (Sigma's dead panel)^T
+    bTrsm.s0 = f.sMat, bTrsm.s1 = f.sBlk, bTrsm.s2 = f.sBlk, bTrsm.s3 = f.sSc, bTrsm.s4 = f.sCv, bTrsm.s5 = f.sVec;
+    bVt.s0 = bVt.s1 = f.sL, bVt.s2 = f.sMat, bVt.s3 = f.sMat;                 // Sigma' (+= K the first time) -= Vt Vt^T
+    int *flag_err = ep->flags + np / GP_NB;        // problem 0's error word collects every problem's
+    const int token = ++ep->epoch;
+    const int utarget = urgent ? ++ep->uepoch : 0;
+    // Only the TRAILING part of the recurrence is carried: the sites after a block read mu_i and Sigma_ii "as of now",
+    // which depend on the earlier blocks through rows/columns >= their own block only, and the end-of-sweep
+    // refactorisation (:56-61) rebuilds Sigma and mu from the site parameters anyway.  So the delayed columns
+    // S = Sigma0[r0:, blk] Lmat^-T, the mean update mu[r0:] += S coef and the rank-128 update
+    // Sigma[r0:, r0:] -= S diag(c) S^T cover rows/columns r0 = i0 + 128 onwards (lower triangle) -- n^3/3 flops per
+    // sweep on the MFMA syrk instead of 2 n^3 on full-square updates.  The block's own column panel of Sigma is dead after
+    // the block, so the panel solve runs in place on it; the same launch writes the scaled copy S diag(c) and adds S coef
+    // to the mean (row dot fused into the panel solve).
+    //
+    // Two streams.  The serial chain -- block kernel b (one workgroup, ~110 us) -> the 128 rows of S that belong to block
+    // b+1 -> the ONE 128 x 128 tile of the update block kernel b+1 reads -> block kernel b+1 -- stays on the main stream;
+    // the rest of block b's panel solve and rank-128 update (all rows from block b+2 on) runs on the side stream UNDER block
+    // kernel b+1.  The side stream is CU-masked (gp_ctx_create), so the block kernel, which needs most of a CU's LDS,
+    // always finds a free CU.  Small per-block buffers (Lmat, tile inverses, c, coef) alternate by block parity: the
+    // side stream still reads block b's while block kernel b+1 writes its own.
+    //
+    // Third stream: the refactorisation of :56-61 runs UNDER the site loop, one block behind it.  A site is visited once per
+    // sweep, so block b's precisions are final when block kernel b ends; with the factor written as chol(B) = S^1/2 chol(K + S^-1)
+    // (ep_winit_kernel) column block b of the right-looking factorisation needs exactly those and nothing later.  Per block:
+    // scale block b's rows and columns of the working matrix, one step of the two-level Cholesky with the np rows of K S^1/2
+    // riding along (-> Vt[:, b] = ((K S^1/2) L^-T)[:, b]), and the rank-128 update  Sigma_next -= Vt[:, b] Vt[:, b]^T  of the
+    // NEXT covariance (second buffer; the site loop still works in the current one).  What is left after the last block
+    // kernel is the last block's own step and mu = Sigma nu.
+    if (pipe) {
+        GP_HIP(ctx, hipEventRecord(ep->ev_w, s));
+        GP_HIP(ctx, hipStreamWaitEvent(s3, ep->ev_w, 0));
+        GP_HIP(ctx, hipStreamWaitEvent(s4, ep->ev_w, 0));
+        hipLaunchKernelGGL(ep_winit_kernel, dim3(8, np < 4096 ? np : 4096, count), dim3(256), 0, s3, ep->L, ldl, ep->K, np, f.sL, f.sMat);
+    }
+    int b = 0, pend0 = 0;   // pend0: first column of Vt not yet in the next covariance
+    hipEvent_t last_side = nullptr;
+    for (int i0 = 0; i0 < n; i0 += GP_NB, ++b) {
+        const int bsz = (n - i0 < GP_NB) ? n - i0 : GP_NB;
+        const int par = b & 1;
+        double *Lmat = ep->blk + (size_t)par * EP_BLK_ELEMS, *bdinv = Lmat + GP_NB * GP_NB;
+        double *cvec = ep->cvec + (size_t)par * 2 * GP_NB, *ncoef = cvec + GP_NB;   // c and coef of every site of the block
+        if (fused) {
+            // the prologue reads Sigma[blk b, blk b-1 .. b]: entries the side stream's update of block b-2 wrote.  With urgent tiles
+            // (GPCORE_EP_URGENT, default) the kernel is launched WITHOUT waiting for that launch to finish: the update announces those
+            // two tiles with a counter the moment they are stored, and the prologue waits for the counter (bounded).  The chain then
+            // never waits for the rest of a 500-tile update it does not read -- the block periods of 200-260 us in the first half of
+            // a sweep (profiles/r03_j_c4_sweep_summary.txt) were exactly that.  (Computing the two tiles in a kernel of their own ahead
+            // of the update -- 100 one-wave workgroups that need no LDS slot -- was measured too: 190.8 against 197.0 sweeps/s without
+            // any urgent tiles on the same box; one more launch on the side stream costs more than the earlier tiles gain.)
+            const bool uw = urgent && b >= 2;
+            if (b >= 2 && !uw) GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev[4 * (b - 2) + 2], 0));
+            if (b > 0)
+                hipLaunchKernelGGL(ep_block2_kernel<true>, dim3(count), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, ep->Sig, ep->vec,
+                                   ep->y, ep->blk, ep->cvec, ep->Sc, ep->flags, par, token, es, ((b - 1) % (EP_OUTER / GP_NB)) * GP_NB * np,
+                                   uw ? ep->uflags + (b - 2) : nullptr, 2 * utarget, f.uerr);
+            else
+                hipLaunchKernelGGL(ep_block2_kernel<false>, dim3(count), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, ep->Sig, ep->vec,
+                                   ep->y, ep->blk, ep->cvec, ep->Sc, ep->flags, par, token, es, 0, nullptr, 0, nullptr);
+        } else
+            hipLaunchKernelGGL(ep_block1_kernel, dim3(1), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK1_LDS, s, n, np, i0, bsz, ep->Sig, ep->mu(), ep->y,
+                               ep->tau(), ep->nu(), ep->cav_tau(), ep->cav_nu(), cvec, ncoef, Lmat, bdinv);
+        hipEvent_t ev_fac = ep->ev[4 * b], ev_rows = ep->ev[4 * b + 1], ev_side = ep->ev[4 * b + 2], ev_vt = ep->ev[4 * b + 3];
+        if (overlap) GP_HIP(ctx, hipEventRecord(ev_fac, s));
+        if (pipe) {
+            // refactorisation under the site loop, one block behind it (third and fourth stream)
+            GP_HIP(ctx, hipStreamWaitEvent(s3, ev_fac, 0));
+            {
+                const int gx = (2 * np - i0 + 1023) / 1024;
+                hipLaunchKernelGGL(ep_wscale_kernel, dim3(gx, GP_NB + std::min((i0 / 2 + gx - 1) / gx, 256), count), dim3(256), 0, s3, ep->L, ldl, np, i0,
+                                   ep->tau(), n, ep->st(), f.sL, f.sVec);
+            }
+            gpi_chol_panel_step(ctx, s3, ep->L, np, ldl, ep->dinv, np, i0, ev_vt, f.far_split ? s4 : nullptr, ep->ev_parta, count, f.sL, f.sDinv, f.info);
+            // the finished columns of Vt go into the next covariance on a stream of their own, two blocks (K = 256) at a time (sig_blocks);
+            // the last two blocks one by one so that only a K = 128 update is left after the last block kernel
+            if ((b + 1) % f.sig_blocks == 0 || b >= nblk - 2) {
+                GP_HIP(ctx, hipStreamWaitEvent(s4, ev_vt, 0));
+                const int kw = i0 + GP_NB - pend0;
+                const double *Vb = ep->L + np + (size_t)pend0 * ldl;
+                gp_prof_begin(ctx, GP_PROF_SYRK, s4);
+                gpk_gemm_nt(s4, np, np, kw, -1.0, Vb, ldl, Vb, ldl, 1.0, ep->Sig2, np, 1, 0, bVt, pend0 == 0 ? ep->K : nullptr, np);
+                gp_prof_end(ctx, GP_PROF_SYRK, (double)count * np * ((double)np + GP_NB) * kw, s4);
+                pend0 = i0 + GP_NB;
+            }
+        }
+        if (fused && b > 0) {
+            // side stream: block b-1's whole trailing update, Sigma[i0:, i0:] -= Sc S^T (lower), in ONE launch.  Its operands' first
+            // 128 rows are what this kernel's prologue has just solved: announced by a device flag, awaited by a one-thread kernel
+            // (enqueued AFTER the producer, which depends on nothing later on any stream; the wait is bounded and reports instead
+            // of hanging).  The rows below were solved by the side stream itself in the iteration before.  (The tile of this
+            // block itself, which the chain keeps in LDS, is updated here too -- nobody reads it again -- so that the product is
+            // one lower-trapezoid launch.)  Every launch on this stream costs ~40 us while the other streams' GEMMs hold the CUs,
+            // whatever its size (profiles/r03_d_sweep_urgent_first.txt), so the chain's slack is spent on three launches per block
+            // (solve, wait, update), not on five.  (A batch: every problem's update after every problem's flag.)
+            if (np - i0 > GP_NB) {
+                hipLaunchKernelGGL(ep_wait_flag_kernel, dim3(count), dim3(1), 0, s2, ep->flags + b, f.sFlag, token, flag_err);
+                ep_trailing_update(ctx, s2, np, i0, ep->Sc, ep->Sig, bSig, urgent ? ep->uflags + (b - 1) : nullptr);
+            }
+            GP_HIP(ctx, hipEventRecord(ep->ev[4 * (b - 1) + 2], s2));
+            last_side = ep->ev[4 * (b - 1) + 2];
+        }
+        const int r0 = i0 + GP_NB, rt = np - r0;
+        if (rt <= 0 || r0 >= n) continue;
+        double *St = ep->Sig + (size_t)r0 + (size_t)i0 * np;
+        double *Sct = ep->Sc + (fused ? (size_t)(b % (EP_OUTER / GP_NB)) * GP_NB * np : (size_t)0) + r0;   // fused: the block's column block of the panel
+        double *Ctr = ep->Sig + (size_t)r0 + (size_t)r0 * np;
+        if (!overlap) {
+            gpk_trsm_panel128(s, St, rt, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0, gp_batch(), Sct, cvec);
+            gp_prof_begin(ctx, GP_PROF_GEMM);
+            gpk_gemm_nt(s, rt, rt, GP_NB, -1.0, Sct, np, St, np, 1.0, Ctr, np, 1);
+            gp_prof_end(ctx, GP_PROF_GEMM, (double)rt * ((double)rt + GP_NB) * GP_NB);
+            continue;
+        }
+        const int rest = rt - GP_NB;            // rows from block b+2 on
+        if (rest > 0) {
+            GP_HIP(ctx, hipStreamWaitEvent(s2, ev_fac, 0));
+            // side stream, part 1: rows [r0+128, np) of the panel solve and their own lower triangle of the update
+            gpk_trsm_panel128(s2, St + GP_NB, rest, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0 + GP_NB, bTrsm, Sct + GP_NB, cvec);
+            if (!fused) {
+                gp_prof_begin(ctx, GP_PROF_GEMM, s2);
+                gpk_gemm_nt(s2, rest, rest, GP_NB, -1.0, Sct + GP_NB, np, St + GP_NB, np, 1.0, Ctr + GP_NB + (size_t)GP_NB * np, np, 1);
+                gp_prof_end(ctx, GP_PROF_GEMM, (double)rest * ((double)rest + GP_NB) * GP_NB, s2);
+            }
+        }
+        if (fused) continue;     // the link is the next block kernel's prologue, part 2 follows its flag (above)
+        // main stream: the 128 rows of block b+1 -- they read Sigma entries the side stream's update of block b-1 wrote
+        if (b > 0) GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev[4 * (b - 1) + 2], 0));
+        if (f.fused_link) gpk_ep_link(s, St, np, Lmat, bdinv, ncoef, ep->mu() + r0, Sct, cvec, Ctr, np);
+        else {
+            gpk_trsm_panel128(s, St, GP_NB, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0, gp_batch(), Sct, cvec);
+            hipLaunchKernelGGL(ep_diag_update_kernel, dim3(36), dim3(64), 0, s, Ctr, np, Sct, St, np);
+        }
+        if (rest > 0) {
+            GP_HIP(ctx, hipEventRecord(ev_rows, s));
+            GP_HIP(ctx, hipStreamWaitEvent(s2, ev_rows, 0));
+            // side stream, part 2: column panel of block b+1 below its diagonal tile (needs the rows the main stream just solved)
+            gpk_gemm_nt(s2, rest, GP_NB, GP_NB, -1.0, Sct + GP_NB, np, St, np, 1.0, Ctr + GP_NB, np, 0);
+        }
+        GP_HIP(ctx, hipEventRecord(ev_side, s2));
+        last_side = ev_side;
+    }
+    if (last_side) GP_HIP(ctx, hipStreamWaitEvent(s, last_side, 0));   // the refactorisation rewrites Sigma and mu
+    if (pipe) {
+        GP_HIP(ctx, hipEventRecord(ep->ev_pipe, s4));   // s4's last update waited for s3's last panel solve
+        GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev_pipe, 0));
+        GP_HIP(ctx, hipEventRecord(ep->ev_chol, s3));   // (the last step has no update after its solve; kept for symmetry)
+        GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev_chol, 0));
+        // every view of a slab changes buffers, the ones outside this launch too: view g stays g strides behind problem 0
+        for (int g = 0; g < nep; ++g) { std::swap(eps[g]->Sig, eps[g]->Sig2); eps[g]->sig_mirrored = false; }
+        ep_symv_lower(s, ep->Sig, np, np, ep->nu(), f.partial, ep->mu(), 0, np, count, f.sMat, f.sVec, f.sPart);
+    } else {
+        GP_TRY(ep_refactor(ep));
+    }
+    GP_LAUNCH_CHECK(ctx);
+    for (int g = 0; g < count; ++g) eps[g]->sweeps += 1;
+    return GP_OK;
+}
+
+// ONE sweep of problems 0 .. count-1 of the slab: the fused chain + streamed refactorisation of a single run, with a batch's knobs.
+gp_status ep_slab_sweep(ep_slab &sl, int count) {
     gp_ctx *ctx = sl.ctx;
     GP_TRY(gpi_ctx_ep_streams(ctx));
     gp_ep *e0 = sl.ep[0];
-    for (int g = 0; g < count; ++g) sl.ep[g]->lw_valid = false;     // every problem's L is rewritten
+    ep_sweep_form f;
+    f.count = count, f.info = sl.info, f.partial = sl.partial;
+    f.sMat = sl.sMat(), f.sL = sl.sL(), f.sVec = sl.sVec(), f.sBlk = sl.sBlk(), f.sCv = sl.sCv(), f.sSc = sl.sSc(), f.sDinv = sl.sDinv();
+    f.sPart = sl.sPart(), f.sFlag = sl.sFlag();
+    f.pipe = f.fused = true;      // urgent stays off: uflags is one problem's worth
     // The fourth stream is CU-masked for the single run's sake (64 CUs kept free of its long GEMMs so that the chain's small kernels
     // find a CU); a batch is bound by GEMM throughput instead and loses by the mask (12 problems at n = 4096, aggregate sweeps/s with
     // 0 / 32 / 64 / 96 CUs reserved: 289 / 281 / 271 / 245), so its long GEMMs go to the unmasked third stream behind the factorisation
     // chain from np = 4096 on (n = 4096: 287.6 against 272.1 sweeps/s aggregate; n = 8192: 39.8 either way; below that the fourth stream
     // pays: n = 2048 1669 against 1559).  GPCORE_EP_LOCK_S4 = 0 / 1 forces.
     const bool own_s4 = [np = sl.np] { const char *e = getenv("GPCORE_EP_LOCK_S4"); return e ? atoi(e) != 0 : np < 4096; }();
-    hipStream_t s = ctx->stream, s2 = ctx->side, s3 = ctx->side2, s4 = own_s4 ? ctx->side3 : ctx->side2;
-    const int n = sl.n, np = sl.np, nblk = np / GP_NB, ldl = e0->ldl;
+    f.s4 = own_s4 ? ctx->side3 : ctx->side2;
     // columns of Vt per next-covariance update: a batch is bound by GEMM throughput, not by the chain, so long updates pay (n = 4096,
     // 12 problems, K = 256 / 512 / 1024: 229 / 239 / 244 sweeps/s aggregate)
-    const int sig_blocks = [np] { const int v = gp_env_blocks("GPCORE_EP_SIG_K"); return v >= GP_NB ? v / GP_NB : (np >= 4096 ? 8 : 2); }();
-    const bool far_split = [] { const char *e = getenv("GPCORE_EP_FAR"); return !e || atoi(e) != 0; }();
-    ep_strides es;
-    es.sig = sl.sMat(), es.vec = sl.sVec(), es.y = 0, es.blk = sl.sBlk(), es.cvec = sl.sCv(), es.sc = sl.sSc(), es.flag = sl.sFlag();
-    gp_batch bSig, bTrsm, bVt;
-    bSig.count = bTrsm.count = bVt.count = count;
-    bSig.s0 = sl.sSc(), bSig.s1 = sl.sMat(), bSig.s2 = sl.sMat();                      // C (Sigma) -= A (Sc) B (Sigma's dead panel)^T
-    bTrsm.s0 = sl.sMat(), bTrsm.s1 = sl.sBlk(), bTrsm.s2 = sl.sBlk(), bTrsm.s3 = sl.sSc(), bTrsm.s4 = sl.sCv(), bTrsm.s5 = sl.sVec();
-    bVt.s0 = bVt.s1 = sl.sL(), bVt.s2 = sl.sMat(), bVt.s3 = sl.sMat();                 // Sigma' (+= K the first time) -= Vt Vt^T
-    const int token = ++e0->epoch;
-    int *flag_err = e0->flags + np / GP_NB;        // problem 0's error word collects every problem's
-    GP_HIP(ctx, hipMemsetAsync(sl.info, 0, sizeof(int) * count, s));
-    GP_HIP(ctx, hipMemsetAsync(flag_err, 0, sizeof(int), s));
-    GP_HIP(ctx, hipEventRecord(e0->ev_w, s));
-    GP_HIP(ctx, hipStreamWaitEvent(s3, e0->ev_w, 0));
-    GP_HIP(ctx, hipStreamWaitEvent(s4, e0->ev_w, 0));
-    hipLaunchKernelGGL(ep_winit_kernel, dim3(8, np < 4096 ? np : 4096, count), dim3(256), 0, s3, e0->L, ldl, e0->K, np, sl.sL(), sl.sMat());
-    int b = 0, pend0 = 0;
-    hipEvent_t last_side = nullptr;
-    for (int i0 = 0; i0 < n; i0 += GP_NB, ++b) {
-        const int bsz = (n - i0 < GP_NB) ? n - i0 : GP_NB;
-        const int par = b & 1;
-        double *Lmat = e0->blk + (size_t)par * EP_BLK_ELEMS, *bdinv = Lmat + GP_NB * GP_NB;
-        double *cvec = e0->cvec + (size_t)par * 2 * GP_NB, *ncoef = cvec + GP_NB;
-        if (b >= 2) GP_HIP(ctx, hipStreamWaitEvent(s, e0->ev[4 * (b - 2) + 2], 0));
-        if (b > 0)
-            hipLaunchKernelGGL(ep_block2_kernel<true>, dim3(count), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, e0->Sig, e0->vec, e0->y,
-                               e0->blk, e0->cvec, e0->Sc, e0->flags, par, token, es, ((b - 1) % (EP_OUTER / GP_NB)) * GP_NB * np, nullptr, 0, nullptr);
-        else
-            hipLaunchKernelGGL(ep_block2_kernel<false>, dim3(count), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, e0->Sig, e0->vec, e0->y,
-                               e0->blk, e0->cvec, e0->Sc, e0->flags, par, token, es, 0, nullptr, 0, nullptr);
-        hipEvent_t ev_fac = e0->ev[4 * b], ev_vt = e0->ev[4 * b + 3];
-        GP_HIP(ctx, hipEventRecord(ev_fac, s));
-        // refactorisation under the site loop, one block behind it (third and fourth stream)
-        GP_HIP(ctx, hipStreamWaitEvent(s3, ev_fac, 0));
-        {
-            const int gx = (2 * np - i0 + 1023) / 1024;
-            hipLaunchKernelGGL(ep_wscale_kernel, dim3(gx, GP_NB + std::min((i0 / 2 + gx - 1) / gx, 256), count), dim3(256), 0, s3, e0->L, ldl, np, i0,
-                               e0->tau(), n, e0->st(), sl.sL(), sl.sVec());
-        }
-        gpi_chol_panel_step(ctx, s3, e0->L, np, ldl, e0->dinv, np, i0, ev_vt, (far_split && own_s4) ? s4 : nullptr, e0->ev_parta, count, sl.sL(), sl.sDinv(), sl.info);
-        if ((b + 1) % sig_blocks == 0 || b >= nblk - 2) {
-            GP_HIP(ctx, hipStreamWaitEvent(s4, ev_vt, 0));
-            const int kw = i0 + GP_NB - pend0;
-            const double *Vb = e0->L + np + (size_t)pend0 * ldl;
-            gp_prof_begin(ctx, GP_PROF_SYRK, s4);
-            gpk_gemm_nt(s4, np, np, kw, -1.0, Vb, ldl, Vb, ldl, 1.0, e0->Sig2, np, 1, 0, bVt, pend0 == 0 ? e0->K : nullptr, np);
-            gp_prof_end(ctx, GP_PROF_SYRK, (double)count * np * ((double)np + GP_NB) * kw, s4);
-            pend0 = i0 + GP_NB;
-        }
-        if (b > 0) {
-            // second stream: block b-1's trailing update of every problem, after every problem's flag
-            if (np - i0 > GP_NB) {
-                hipLaunchKernelGGL(ep_wait_flag_kernel, dim3(count), dim3(1), 0, s2, e0->flags + b, sl.sFlag(), token, flag_err);
-                ep_trailing_update(ctx, s2, np, i0, e0->Sc, e0->Sig, bSig);
-            }
-            GP_HIP(ctx, hipEventRecord(e0->ev[4 * (b - 1) + 2], s2));
-            last_side = e0->ev[4 * (b - 1) + 2];
-        }
-        const int r0 = i0 + GP_NB, rt = np - r0;
-        if (rt <= 0 || r0 >= n) continue;
-        const int rest = rt - GP_NB;
-        if (rest > 0) {
-            double *St = e0->Sig + (size_t)r0 + (size_t)i0 * np, *Sct = e0->Sc + (size_t)(b % (EP_OUTER / GP_NB)) * GP_NB * np + r0;
-            GP_HIP(ctx, hipStreamWaitEvent(s2, ev_fac, 0));
-            gpk_trsm_panel128(s2, St + GP_NB, rest, np, Lmat, GP_NB, bdinv, nullptr, ncoef, e0->mu() + r0 + GP_NB, bTrsm, Sct + GP_NB, cvec);
-        }
-    }
-    if (last_side) GP_HIP(ctx, hipStreamWaitEvent(s, last_side, 0));
-    GP_HIP(ctx, hipEventRecord(e0->ev_pipe, s4));
-    GP_HIP(ctx, hipStreamWaitEvent(s, e0->ev_pipe, 0));
-    GP_HIP(ctx, hipEventRecord(e0->ev_chol, s3));
-    GP_HIP(ctx, hipStreamWaitEvent(s, e0->ev_chol, 0));
-    for (gp_ep *v : sl.ep) { std::swap(v->Sig, v->Sig2); v->sig_mirrored = false; }
-    ep_symv_lower(s, e0->Sig, np, np, e0->nu(), sl.partial, e0->mu(), 0, np, count, sl.sMat(), sl.sVec(), sl.sPart());
-    GP_LAUNCH_CHECK(ctx);
-    for (int g = 0; g < count; ++g) sl.ep[g]->sweeps += 1;
-    return GP_OK;
+    f.sig_blocks = [np = sl.np] { const int v = gp_env_blocks("GPCORE_EP_SIG_K"); return v >= GP_NB ? v / GP_NB : (np >= 4096 ? 8 : 2); }();
+    f.far_split = own_s4 && [] { const char *e = getenv("GPCORE_EP_FAR"); return !e || atoi(e) != 0; }();
+    GP_HIP(ctx, hipMemsetAsync(sl.info, 0, sizeof(int) * count, ctx->stream));
+    GP_HIP(ctx, hipMemsetAsync(e0->flags + sl.np / GP_NB, 0, sizeof(int), ctx->stream));     // problem 0's error word collects every problem's
+    return ep_sweep_once(sl.ep.data(), (int)sl.ep.size(), f);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1289,7 +1224,6 @@ gp_status gp_ep_sweep(gp_ep *ep, int nsweeps, double *tau, double *nu, int *info
     hipStream_t s = ctx->stream;
     const int n = ep->n, np = ep->np;
     if (info) *info = 0;
-    if (nsweeps > 0) ep->lw_valid = false;     // every sweep ends with a new L (both refactorisation forms)
     GP_HIP(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), s));
     // GPCORE_EP_OVERLAP=0: every launch of a site block on one stream (the form the overlapped one is tested against)
     const bool overlap = [] { const char *e = getenv("GPCORE_EP_OVERLAP"); return !e || atoi(e) != 0; }();
@@ -1297,7 +1231,6 @@ gp_status gp_ep_sweep(gp_ep *ep, int nsweeps, double *tau, double *nu, int *info
     // it: n = 1024 552 / 592, n = 2048 382 / 265, n = 4096 162 / 102, n = 8192 29.1 / 27.2)
     const bool pipe = overlap && np >= 2 * GP_NB && [np] { const char *e = getenv("GPCORE_EP_PIPELINE"); return e ? atoi(e) != 0 : np > 1024; }();
     if (pipe) GP_TRY(gpi_ctx_ep_streams(ctx));
-    hipStream_t s2 = ctx->side, s3 = ctx->side2, s4 = ctx->side3;
     // The link between two block kernels as ONE launch (gpk_ep_link) or as panel solve + tile update on 2 + 36 workgroups: alone the two
     // launches are faster (the single workgroup is bound by one CU's matrix pipe: n = 4096 end-of-sweep form 106.9 vs 103.3 sweeps/s),
     // under the streamed refactorisation's GEMMs the fused one is (167.4 vs 163.9) -- so it follows `pipe` (GPCORE_EP_LINK overrides)
@@ -1306,18 +1239,17 @@ gp_status gp_ep_sweep(gp_ep *ep, int nsweeps, double *tau, double *nu, int *info
     // chain; 0: block kernel + link kernel (the form it is tested against, bit for bit).  Measured (sweeps/s fused / two launches):
     // n = 4096 181.0 / 182.1, n = 2048 425.5 / 411.8, n = 1024 627.0 / 668.3 -- the prologue costs what the link kernel did (34 us:
     // profiles/r03_c_sweep_fused.txt), the chain is as much bound by the side stream's solve + updates as by its own kernels, so
-    // the default follows the streamed refactorisation (np > 1024); the lockstep batch (ep_sweep_lockstep) always uses it
+    // the default follows the streamed refactorisation (np > 1024); the lockstep batch (ep_slab_sweep) always uses it
     const bool fused = overlap && [pipe] { const char *e = getenv("GPCORE_EP_FUSED"); return e ? atoi(e) != 0 : pipe; }();
     int *flag_err = ep->flags + np / GP_NB;
     if (fused) GP_HIP(ctx, hipMemsetAsync(flag_err, 0, sizeof(int), s));
-    // urgent tiles (see the launch of ep_block2_kernel below)
+    // urgent tiles (see the launch of ep_block2_kernel in ep_sweep_once)
     const bool urgent = fused && [] { const char *e = getenv("GPCORE_EP_URGENT"); return !e || atoi(e) != 0; }();
     const bool far_split = [] { const char *e = getenv("GPCORE_EP_FAR"); return !e || atoi(e) != 0; }();
     // columns of Vt per next-covariance update (GPCORE_EP_SIG_K; n = 4096 sweeps/s at 128 / 256 / 384 / 512 / 1024 / 2048: 173 / 181 / 175 / 177 /
     // 172 / 155 -- short enough to spread the fourth stream's load evenly, long enough for the GEMM)
     // (n = 8192: 29.3 sweeps/s at K = 512 against 28.0 at 256, n = 2048: 423 against 406 -- 512 from np = 6144 on)
     const int sig_blocks = [np] { const int v = gp_env_blocks("GPCORE_EP_SIG_K"); return v >= GP_NB ? v / GP_NB : (np >= 6144 ? 4 : 2); }();
-    const int nblk = np / GP_NB;
     double *partial = nullptr;
     if (pipe) {
         if (!ep->Sig2 && hipMalloc(&ep->Sig2, sizeof(double) * (size_t)np * np) != hipSuccess) {
@@ -1327,158 +1259,11 @@ gp_status gp_ep_sweep(gp_ep *ep, int nsweeps, double *tau, double *nu, int *info
         }
         GP_TRY(gpi_ws_get(ctx, WS_PARTIAL, sizeof(double) * (size_t)(SYMV_CHUNKS + 1) * np, &partial));
     }
-    for (int sw = 0; sw < nsweeps; ++sw) {
-        const int token = ++ep->epoch;
-        const int utarget = urgent ? ++ep->uepoch : 0;
-        // Only the TRAILING part of the recurrence is carried: the sites after a block read mu_i and Sigma_ii "as of now",
-        // which depend on the earlier blocks through rows/columns >= their own block only, and the end-of-sweep
-        // refactorisation (:56-61) rebuilds Sigma and mu from the site parameters anyway.  So the delayed columns
-        // S = Sigma0[r0:, blk] Lmat^-T, the mean update mu[r0:] += S coef and the rank-128 update
-        // Sigma[r0:, r0:] -= S diag(c) S^T cover rows/columns r0 = i0 + 128 onwards (lower triangle) -- n^3/3 flops per
-        // sweep on the MFMA syrk instead of 2 n^3 on full-square updates.  The block's own column panel of Sigma is dead after
-        // the block, so the panel solve runs in place on it; the same launch writes the scaled copy S diag(c) and adds S coef
-        // to the mean (row dot fused into the panel solve).
-        //
-        // Two streams.  The serial chain -- block kernel b (one workgroup, ~110 us) -> the 128 rows of S that belong to block
-        // b+1 -> the ONE 128 x 128 tile of the update block kernel b+1 reads -> block kernel b+1 -- stays on the main stream;
-        // the rest of block b's panel solve and rank-128 update (all rows from block b+2 on) runs on the side stream UNDER block
-        // kernel b+1.  The side stream is CU-masked (gp_ctx_create), so the block kernel, which needs most of a CU's LDS,
-        // always finds a free CU.  Small per-block buffers (Lmat, tile inverses, c, coef) alternate by block parity: the
-        // side stream still reads block b's while block kernel b+1 writes its own.
-        //
-        // Third stream: the refactorisation of :56-61 runs UNDER the site loop, one block behind it.  A site is visited once per
-        // sweep, so block b's precisions are final when block kernel b ends; with the factor written as chol(B) = S^1/2 chol(K + S^-1)
-        // (ep_winit_kernel) column block b of the right-looking factorisation needs exactly those and nothing later.  Per block:
-        // scale block b's rows and columns of the working matrix, one step of the two-level Cholesky with the np rows of K S^1/2
-        // riding along (-> Vt[:, b] = ((K S^1/2) L^-T)[:, b]), and the rank-128 update  Sigma_next -= Vt[:, b] Vt[:, b]^T  of the
-        // NEXT covariance (second buffer; the site loop still works in the current one).  What is left after the last block
-        // kernel is the last block's own step and mu = Sigma nu.
-        if (pipe) {
-            GP_HIP(ctx, hipEventRecord(ep->ev_w, s));
-            GP_HIP(ctx, hipStreamWaitEvent(s3, ep->ev_w, 0));
-            GP_HIP(ctx, hipStreamWaitEvent(s4, ep->ev_w, 0));
-            hipLaunchKernelGGL(ep_winit_kernel, dim3(8, np < 4096 ? np : 4096), dim3(256), 0, s3, ep->L, ep->ldl, ep->K, np);
-        }
-        int b = 0, pend0 = 0;   // pend0: first column of Vt not yet in the next covariance
-        hipEvent_t last_side = nullptr;
-        for (int i0 = 0; i0 < n; i0 += GP_NB, ++b) {
-            const int bsz = (n - i0 < GP_NB) ? n - i0 : GP_NB;
-            const int par = b & 1;
-            double *Lmat = ep->blk + (size_t)par * (GP_NB * GP_NB + 8 * 256), *bdinv = Lmat + GP_NB * GP_NB;
-            double *cvec = ep->cvec + (size_t)par * 2 * GP_NB, *ncoef = cvec + GP_NB;   // c and coef of every site of the block
-            if (fused) {
-                // the prologue reads Sigma[blk b, blk b-1 .. b]: entries the side stream's update of block b-2 wrote.  With urgent tiles
-                // (GPCORE_EP_URGENT, default) the kernel is launched WITHOUT waiting for that launch to finish: the update announces those
-                // two tiles with a counter the moment they are stored, and the prologue waits for the counter (bounded).  The chain then
-                // never waits for the rest of a 500-tile update it does not read -- the block periods of 200-260 us in the first half of
-                // a sweep (profiles/r03_j_c4_sweep_summary.txt) were exactly that.  (Computing the two tiles in a kernel of their own ahead
-                // of the update -- 100 one-wave workgroups that need no LDS slot -- was measured too: 190.8 against 197.0 sweeps/s without
-                // any urgent tiles on the same box; one more launch on the side stream costs more than the earlier tiles gain.)
-                const bool uw = urgent && b >= 2;
-                if (b >= 2 && !uw) GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev[4 * (b - 2) + 2], 0));
-                if (b > 0)
-                    hipLaunchKernelGGL(ep_block2_kernel<true>, dim3(1), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, ep->Sig, ep->vec,
-                                       ep->y, ep->blk, ep->cvec, ep->Sc, ep->flags, par, token, ep_strides(), ((b - 1) % (EP_OUTER / GP_NB)) * GP_NB * np,
-                                       uw ? ep->uflags + (b - 2) : nullptr, 2 * utarget, flag_err);
-                else
-                    hipLaunchKernelGGL(ep_block2_kernel<false>, dim3(1), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK2_LDS, s, n, np, i0, bsz, ep->Sig, ep->vec,
-                                       ep->y, ep->blk, ep->cvec, ep->Sc, ep->flags, par, token, ep_strides(), 0, nullptr, 0, nullptr);
-            } else
-                hipLaunchKernelGGL(ep_block1_kernel, dim3(1), dim3(64 * EP_BLOCK1_WAVES), EP_BLOCK1_LDS, s, n, np, i0, bsz, ep->Sig, ep->mu(), ep->y,
-                                   ep->tau(), ep->nu(), ep->cav_tau(), ep->cav_nu(), cvec, ncoef, Lmat, bdinv);
-            hipEvent_t ev_fac = ep->ev[4 * b], ev_rows = ep->ev[4 * b + 1], ev_side = ep->ev[4 * b + 2], ev_vt = ep->ev[4 * b + 3];
-            if (overlap) GP_HIP(ctx, hipEventRecord(ev_fac, s));
-            if (pipe) {
-                GP_HIP(ctx, hipStreamWaitEvent(s3, ev_fac, 0));
-                {
-                    const int gx = (2 * np - i0 + 1023) / 1024;
-                    hipLaunchKernelGGL(ep_wscale_kernel, dim3(gx, GP_NB + std::min((i0 / 2 + gx - 1) / gx, 256)), dim3(256), 0, s3, ep->L, ep->ldl, np, i0,
-                                       ep->tau(), n, ep->st());
-                }
-                gpi_chol_panel_step(ctx, s3, ep->L, np, ep->ldl, ep->dinv, np, i0, ev_vt, far_split ? s4 : nullptr, ep->ev_parta);
-                // the finished columns of Vt go into the next covariance on a stream of their own, two blocks (K = 256) at a time;
-                // the last two blocks one by one so that only a K = 128 update is left after the last block kernel
-                if ((b + 1) % sig_blocks == 0 || b >= nblk - 2) {
-                    GP_HIP(ctx, hipStreamWaitEvent(s4, ev_vt, 0));
-                    const int kw = i0 + GP_NB - pend0;
-                    const double *Vb = ep->L + np + (size_t)pend0 * ep->ldl;
-                    gp_prof_begin(ctx, GP_PROF_SYRK, s4);
-                    gpk_gemm_nt(s4, np, np, kw, -1.0, Vb, ep->ldl, Vb, ep->ldl, 1.0, ep->Sig2, np, 1, 0, gp_batch(), pend0 == 0 ? ep->K : nullptr, np);
-                    gp_prof_end(ctx, GP_PROF_SYRK, (double)np * ((double)np + GP_NB) * kw, s4);
-                    pend0 = i0 + GP_NB;
-                }
-            }
-            if (fused && b > 0) {
-                // side stream: block b-1's whole trailing update, Sigma[i0:, i0:] -= Sc S^T (lower), in ONE launch.  Its operands' first
-                // 128 rows are what this kernel's prologue has just solved: announced by a device flag, awaited by a one-thread kernel
-                // (enqueued AFTER the producer, which depends on nothing later on any stream; the wait is bounded and reports instead
-                // of hanging).  The rows below were solved by the side stream itself in the iteration before.  (The tile of this
-                // block itself, which the chain keeps in LDS, is updated here too -- nobody reads it again -- so that the product is
-                // one lower-trapezoid launch.)  Every launch on this stream costs ~40 us while the other streams' GEMMs hold the CUs,
-                // whatever its size (profiles/r03_d_sweep_urgent_first.txt), so the chain's slack is spent on three launches per block
-                // (solve, wait, update), not on five.
-                if (np - i0 > GP_NB) {
-                    hipLaunchKernelGGL(ep_wait_flag_kernel, dim3(1), dim3(1), 0, s2, ep->flags + b, 0, token, flag_err);
-                    ep_trailing_update(ctx, s2, np, i0, ep->Sc, ep->Sig, gp_batch(), urgent ? ep->uflags + (b - 1) : nullptr);
-                }
-                GP_HIP(ctx, hipEventRecord(ep->ev[4 * (b - 1) + 2], s2));
-                last_side = ep->ev[4 * (b - 1) + 2];
-            }
-            const int r0 = i0 + GP_NB, rt = np - r0;
-            if (rt <= 0 || r0 >= n) continue;
-            double *St = ep->Sig + (size_t)r0 + (size_t)i0 * np;
-            double *Sct = ep->Sc + (fused ? (size_t)(b % (EP_OUTER / GP_NB)) * GP_NB * np : (size_t)0) + r0;   // fused: the block's column block of the panel
-            double *Ctr = ep->Sig + (size_t)r0 + (size_t)r0 * np;
-            if (!overlap) {
-                gpk_trsm_panel128(s, St, rt, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0, gp_batch(), Sct, cvec);
-                gp_prof_begin(ctx, GP_PROF_GEMM);
-                gpk_gemm_nt(s, rt, rt, GP_NB, -1.0, Sct, np, St, np, 1.0, Ctr, np, 1);
-                gp_prof_end(ctx, GP_PROF_GEMM, (double)rt * ((double)rt + GP_NB) * GP_NB);
-                continue;
-            }
-            const int rest = rt - GP_NB;            // rows from block b+2 on
-            if (rest > 0) {
-                GP_HIP(ctx, hipStreamWaitEvent(s2, ev_fac, 0));
-                // side stream, part 1: rows [r0+128, np) of the panel solve and their own lower triangle of the update
-                gpk_trsm_panel128(s2, St + GP_NB, rest, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0 + GP_NB, gp_batch(), Sct + GP_NB, cvec);
-                if (!fused) {
-                    gp_prof_begin(ctx, GP_PROF_GEMM, s2);
-                    gpk_gemm_nt(s2, rest, rest, GP_NB, -1.0, Sct + GP_NB, np, St + GP_NB, np, 1.0, Ctr + GP_NB + (size_t)GP_NB * np, np, 1);
-                    gp_prof_end(ctx, GP_PROF_GEMM, (double)rest * ((double)rest + GP_NB) * GP_NB, s2);
-                }
-            }
-            if (fused) continue;     // the link is the next block kernel's prologue, part 2 follows its flag (above)
-            // main stream: the 128 rows of block b+1 -- they read Sigma entries the side stream's update of block b-1 wrote
-            if (b > 0) GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev[4 * (b - 1) + 2], 0));
-            if (fused_link) gpk_ep_link(s, St, np, Lmat, bdinv, ncoef, ep->mu() + r0, Sct, cvec, Ctr, np);
-            else {
-                gpk_trsm_panel128(s, St, GP_NB, np, Lmat, GP_NB, bdinv, nullptr, ncoef, ep->mu() + r0, gp_batch(), Sct, cvec);
-                hipLaunchKernelGGL(ep_diag_update_kernel, dim3(36), dim3(64), 0, s, Ctr, np, Sct, St, np);
-            }
-            if (rest > 0) {
-                GP_HIP(ctx, hipEventRecord(ev_rows, s));
-                GP_HIP(ctx, hipStreamWaitEvent(s2, ev_rows, 0));
-                // side stream, part 2: column panel of block b+1 below its diagonal tile (needs the rows the main stream just solved)
-                gpk_gemm_nt(s2, rest, GP_NB, GP_NB, -1.0, Sct + GP_NB, np, St, np, 1.0, Ctr + GP_NB, np, 0);
-            }
-            GP_HIP(ctx, hipEventRecord(ev_side, s2));
-            last_side = ev_side;
-        }
-        if (last_side) GP_HIP(ctx, hipStreamWaitEvent(s, last_side, 0));   // the refactorisation rewrites Sigma and mu
-        if (pipe) {
-            GP_HIP(ctx, hipEventRecord(ep->ev_pipe, s4));   // s4's last update waited for s3's last panel solve
-            GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev_pipe, 0));
-            GP_HIP(ctx, hipEventRecord(ep->ev_chol, s3));   // (the last step has no update after its solve; kept for symmetry)
-            GP_HIP(ctx, hipStreamWaitEvent(s, ep->ev_chol, 0));
-            std::swap(ep->Sig, ep->Sig2);
-            ep_symv_lower(s, ep->Sig, np, np, ep->nu(), partial, ep->mu(), 0, np);
-            ep->sig_mirrored = false;
-        } else {
-            GP_TRY(ep_refactor(ep));
-        }
-        GP_LAUNCH_CHECK(ctx);
-        ep->sweeps += 1;
-    }
+    ep_sweep_form f;
+    f.info = ctx->d_info, f.partial = partial;
+    f.overlap = overlap, f.pipe = pipe, f.fused = fused, f.fused_link = fused_link, f.urgent = urgent, f.far_split = far_split;
+    f.sig_blocks = sig_blocks, f.s4 = ctx->side3, f.uerr = flag_err;
+    for (int sw = 0; sw < nsweeps; ++sw) GP_TRY(ep_sweep_once(&ep, 1, f));
     GP_TRY(ep_join_side(ep));
     // (host time spent enqueueing, measured in round 3: 1.6 ms per 5 ms sweep at n = 4096 -- the host runs three sweeps ahead of the GPU; not launch-bound)
     int h = 0;
@@ -1515,68 +1300,6 @@ gp_status gp_ep_set_site_params(gp_ep *ep, const double *tau, const double *nu, 
     return GP_OK;
 }
 
-gp_status gp_ep_lml(gp_ep *ep, int strict, double *lml) {
-    if (!ep || !lml) return GP_EINVAL;
-    gp_ctx *ctx = ep->ctx;
-    GP_REQUIRE(ctx, ep->sweeps > 0, "no sweep has run yet");
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(ep_lml_kernel, dim3(1), dim3(1024), 0, ctx->stream, ep->n, ep->ldl, ep->L, ep->tau(), ep->nu(), ep->mu(),
-                       ep->cav_tau(), ep->cav_nu(), ep->y, strict, ctx->d_scalars);
-    return gpi_download_2d(ctx, lml, 1, ctx->d_scalars, 1, 1, 1);
-}
-
-static gp_status ep_lml_grad_dev(gp_ep *ep, const double *dX, int d, const double *theta, int strict, double *grad);
-
-gp_status gp_ep_lml_grad_rbf(gp_ep *ep, const double *X, int d, int ldx, const double *theta, int strict, double *grad) {
-    if (!ep) return GP_EINVAL;
-    gp_ctx *ctx = ep->ctx;
-    const int n = ep->n;
-    GP_REQUIRE(ctx, X && theta && grad && d >= 1 && d <= 64 && ldx >= n, "bad arguments (1 <= d <= 64)");
-    GP_REQUIRE(ctx, ep->sweeps > 0, "no sweep has run yet");
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    double *dX;
-    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)n * d, &dX));
-    GP_TRY(gpi_upload_2d(ctx, dX, n, X, ldx, n, d));
-    return ep_lml_grad_dev(ep, dX, d, theta, strict, grad);
-}
-
-// the same with the training inputs already in HBM (n x d, ld = n)
-static gp_status ep_lml_grad_dev(gp_ep *ep, const double *dX, int d, const double *theta, int strict, double *grad) {
-    gp_ctx *ctx = ep->ctx;
-    const int n = ep->n, np = ep->np;
-    hipStream_t s = ctx->stream;
-    const int P = d + 2;
-    double *partial, *parts, *dres;
-    GP_TRY(gpi_ws_get(ctx, WS_PARTIAL, sizeof(double) * (size_t)(SYMV_CHUNKS + 1) * np, &partial));
-    GP_TRY(gpi_ws_get(ctx, WS_SUMSQ, sizeof(double) * (size_t)gpk_lml_grad_partials_size(n, d), &parts));
-    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)(P + 1), &dres));
-    double *t1 = ep->tmp1(), *t2 = ep->tmp2();
-    // rhs = S^1/2 K nu                                                    MarginalLikelihoodEvaluator.scala:53-54
-    gpk_gemv_rows(s, ep->K, n, n, np, ep->nu(), t1, partial, 16);
-    hipLaunchKernelGGL(vec_mul_kernel, g1(n), dim3(256), 0, s, t1, t1, ep->st(), n);
-    const double *Kinv = nullptr;
-    if (strict) {
-        gpi_back_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, t1, t2);                       // temp = L^T \ rhs           :53
-        hipLaunchKernelGGL(vec_div_kernel, g1(n), dim3(256), 0, s, t2, t2, ep->st(), n);   // (S^1/2 L) x = temp  <=>  L x = temp / st
-        gpi_forward_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, t2, t1);                    //                              :55-56
-        hipLaunchKernelGGL(vec_sub_kernel, g1(np), dim3(256), 0, s, t2, ep->nu(), t1, n, np);   // b = nu - x
-    } else {
-        gpi_forward_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, t1, t2);
-        gpi_back_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, t2, t1);
-        hipLaunchKernelGGL(ep_w_kernel, g1(np), dim3(256), 0, s, t2, ep->nu(), ep->st(), t1, n, np);    // b = nu - st o z
-        // R = b b^T - S^1/2 (L L^T)^-1 S^1/2 :  (L L^T)^-1 = T T^T with T = L^-T
-        double *T, *Binv;
-        GP_TRY(gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)np * np, &T));
-        GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)np * np, &Binv));
-        gpi_inverse_transpose_lower(ctx, T, ep->L, np, ep->ldl, ep->dinv);
-        gpk_gemm_nt(s, np, np, np, 1.0, T, np, T, np, 0.0, Binv, np, 1, 1);
-        hipLaunchKernelGGL(scale_sym_lower_kernel, dim3(8, n < 65535 ? n : 65535), dim3(256), 0, s, Binv, ep->st(), n, np);
-        Kinv = Binv;
-    }
-    gpk_lml_grad_traces(s, dX, n, d, n, theta, t2, Kinv, np, parts, dres);    // g_p = 0.5 tr(R C_p), all P parameters  :60-65
-    return gpi_download_2d(ctx, grad, P, dres, P, P, 1);
-}
-
 gp_status gp_ep_get(gp_ep *ep, int what, double *out, int ld) {
     if (!ep || !out) return GP_EINVAL;
     gp_ctx *ctx = ep->ctx;
@@ -1597,367 +1320,6 @@ gp_status gp_ep_get(gp_ep *ep, int what, double *out, int ld) {
         case GP_EP_GET_CAV_NU: return gpi_download_2d(ctx, out, n, ep->cav_nu(), np, n, 1);
         default: GP_SET_ERR(ctx, "unknown selector %d", what); return GP_EINVAL;
     }
-}
-
-gp_status gp_ep_predict(gp_ep *ep, const double *Ks, int m, int ldks, const double *kss_diag, double *prob) {
-    if (!ep) return GP_EINVAL;
-    gp_ctx *ctx = ep->ctx;
-    GP_REQUIRE(ctx, Ks && kss_diag && prob && m >= 0 && ldks >= m, "bad arguments");
-    GP_REQUIRE(ctx, ep->sweeps > 0, "classifier not trained: run gp_ep_sweep first");
-    if (m == 0) return GP_OK;
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int n = ep->n, np = ep->np, mp = gp_pad(m);
-    double *Vt, *partial, *sumsq, *dk, *dout;
-    GP_TRY(gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)mp * np, &Vt));
-    GP_TRY(gpi_ws_get(ctx, WS_PARTIAL, sizeof(double) * (size_t)16 * (mp > np ? mp : np), &partial));
-    GP_TRY(gpi_ws_get(ctx, WS_SUMSQ, sizeof(double) * (size_t)mp, &sumsq));
-    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)mp, &dk));
-    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)2 * mp, &dout));
-    // z = st o L^T \ (L \ (st o (K nu)))                                  GpClassifier.scala:33-36
-    gpk_gemv_rows(s, ep->K, n, n, np, ep->nu(), ep->tmp1(), partial, 16);
-    hipLaunchKernelGGL(vec_mul_kernel, g1(n), dim3(256), 0, s, ep->tmp1(), ep->tmp1(), ep->st(), n);
-    gpi_forward_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp1(), ep->tmp2());
-    gpi_back_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp2(), ep->tmp1());
-    hipLaunchKernelGGL(ep_w_kernel, g1(np), dim3(256), 0, s, ep->tmp2(), ep->nu(), ep->st(), ep->tmp1(), n, np);   // w = nu - z
-    // test-train block: fMean = K* w; V = L \ (st o K*^T) as rows; var = kss - |v|^2    :37-45
-    GP_HIP(ctx, hipMemsetAsync(Vt, 0, sizeof(double) * (size_t)mp * np, s));
-    GP_TRY(gpi_upload_2d(ctx, Vt, mp, Ks, ldks, m, n));
-    GP_HIP(ctx, hipMemcpyAsync(dk, kss_diag, sizeof(double) * m, hipMemcpyHostToDevice, s));
-    gpk_gemv_rows(s, Vt, m, n, mp, ep->tmp2(), dout, partial, 16);
-    hipLaunchKernelGGL(scale_cols_kernel, dim3(1024), dim3(256), 0, s, Vt, mp, Vt, mp, ep->st(), mp, np);
-    GP_HIP(ctx, hipMemsetAsync(sumsq, 0, sizeof(double) * mp, s));
-    gpi_solve_rows_lower(ctx, Vt, mp, ep->L, np, ep->ldl, ep->dinv, sumsq, nullptr, nullptr);
-    hipLaunchKernelGGL(ep_prob_kernel, g1(m), dim3(256), 0, s, dout + mp, dout, sumsq, dk, m);
-    return gpi_download_2d(ctx, prob, m, dout + mp, m, m, 1);
-}
-
-// The classifier from data: K = buildKernelMatrix(GaussianRbfKernel(theta), X) on the device (full, pad identity, sn^2 on the
-// diagonal -- as ep_eval_batched builds it per setting); X and theta stay with the object for gp_ep_predict_rbf.
-gp_status gp_ep_create_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *theta, gp_ep **out) {
-    if (!ctx || !out) return GP_EINVAL;
-    *out = nullptr;
-    GP_REQUIRE(ctx, X && y && theta && n >= 1 && d >= 1 && d <= 64 && ldx >= n, "bad arguments (1 <= d <= 64)");
-    gp_ep *ep = nullptr;
-    GP_TRY(ep_alloc(ctx, n, y, &ep));
-    ep->d = d;
-    ep->theta.assign(theta, theta + d + 2);
-    gp_status st = GP_OK;
-    hipError_t e = hipMalloc(&ep->dX, sizeof(double) * (size_t)n * d);
-    if (e == hipSuccess) e = hipMalloc(&ep->dcen, sizeof(double) * 64);
-    if (e != hipSuccess) { (void)hipGetLastError(); GP_SET_ERR(ctx, "EP training inputs (n=%d, d=%d): %s", n, d, hipGetErrorString(e)); st = GP_ENOMEM; }
-    if (st == GP_OK) st = gpi_upload_2d(ctx, ep->dX, n, X, ldx, n, d);
-    if (st == GP_OK) {
-        gpk_centroid(ctx->stream, ep->dX, n, d, n, ep->dcen);
-        gpk_gram_sym(ctx->stream, ep->dX, n, d, n, ep->theta.data(), ep->K, ep->np, 1, 0.0, gp_gram_flag(ctx), ep->dcen);
-        st = ep_start(ep);     // pad identity, Sigma = K; synchronises, so X is no longer read when this returns
-    }
-    if (st == GP_OK && hipGetLastError() != hipSuccess) { GP_SET_ERR(ctx, "EP Gram build (n=%d, d=%d): launch failed", n, d); st = GP_EHIP; }
-    if (st != GP_OK) { gp_ep_destroy(ep); return st; }
-    *out = ep;
-    return GP_OK;
-}
-
-// GpClassifier.classify (GpClassifier.scala:33-45) from test INPUTS in HBM, batch by batch: cross-Gram into Vt, ONE pass for the
-// latent mean, the column scaling and the pad (ep_mean_scale_kernel), Vt <- Vt L^-T with its row sums of squares, probit epilogue.
-gp_status gp_ep_predict_rbf_dev(gp_ep *ep, const double *dXs, int m, int ldxs, int batch_rows, double *dprob, double *dfmean, double *dfvar) {
-    if (!ep) return GP_EINVAL;
-    gp_ctx *ctx = ep->ctx;
-    GP_REQUIRE(ctx, ep->dX, "classifier was built from a Gram matrix");
-    GP_REQUIRE(ctx, dXs && dprob && m >= 0 && ldxs >= m && batch_rows >= 0, "bad arguments");
-    GP_REQUIRE(ctx, ep->sweeps > 0, "classifier not trained: run gp_ep_sweep first");
-    if (m == 0) return GP_OK;
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int n = ep->n, np = ep->np, d = ep->d;
-    // rows per batch: the rule of gp_predict_dev (Vt under ~32 GiB, at most 131072 rows) unless the caller names one
-    int batch = batch_rows > 0 ? std::max(GP_NB, batch_rows / GP_NB * GP_NB)
-                               : (int)std::min<size_t>(131072, std::max<size_t>(GP_NB, (((size_t)32 << 30) / ((size_t)np * 8)) / GP_NB * GP_NB));
-    batch = std::min(batch, gp_pad(m));
-    double *Vt, *partial, *sumsq, *fm;
-    GP_TRY(gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)batch * np, &Vt));
-    GP_TRY(gpi_ws_get(ctx, WS_PARTIAL, sizeof(double) * (size_t)16 * np, &partial));
-    GP_TRY(gpi_ws_get(ctx, WS_SUMSQ, sizeof(double) * (size_t)batch, &sumsq));
-    GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)batch, &fm));
-    // large batches: the folded factor of the left-looking solve, kept until L changes
-    const double *Lw = nullptr;
-    if (batch / GP_NB >= gpi_rows_left_min()) {
-        if (!ep->Lw) {
-            hipError_t e = hipMalloc(&ep->Lw, sizeof(double) * (size_t)np * np);
-            if (e != hipSuccess) { (void)hipGetLastError(); ep->Lw = nullptr; GP_SET_ERR(ctx, "hipMalloc(Lw, n=%d) failed: %s", n, hipGetErrorString(e)); return GP_ENOMEM; }
-            ep->lw_valid = false;
-        }
-        if (!ep->lw_valid) {
-            double *scratch;
-            GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)np * np, &scratch));
-            gpi_build_lw(ctx, ep->Lw, scratch, ep->L, np, ep->ldl, ep->dinv);
-            ep->lw_valid = true;
-        }
-        Lw = ep->Lw;
-    }
-    // w = nu - st o L^T \ (L \ (st o (K nu))), once per call                  GpClassifier.scala:33-36
-    double *w = ep->tmp2();
-    gpk_gemv_rows(s, ep->K, n, n, np, ep->nu(), ep->tmp1(), partial, 16);
-    hipLaunchKernelGGL(vec_mul_kernel, g1(n), dim3(256), 0, s, ep->tmp1(), ep->tmp1(), ep->st(), n);
-    gpi_forward_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp1(), ep->tmp2());
-    gpi_back_solve_vec(ctx, ep->L, np, ep->ldl, ep->dinv, ep->tmp2(), ep->tmp1());
-    hipLaunchKernelGGL(ep_w_kernel, g1(np), dim3(256), 0, s, w, ep->nu(), ep->st(), ep->tmp1(), n, np);
-    const double sf = ep->theta[0], sn = ep->theta[d + 1];
-    const double kss = sf * sf + sn * sn;      // diagonal of buildKernelMatrix(kernel, X*): the noise is on it
-    for (int lo = 0; lo < m; lo += batch) {
-        const int mb = std::min(batch, m - lo), mp = gp_pad(mb);
-        gp_prof_begin(ctx, GP_PROF_GRAM);
-        gpk_gram_cross(s, dXs + lo, mb, ldxs, ep->dX, n, n, d, ep->theta.data(), Vt, mp, gp_gram_flag(ctx), ep->dcen);
-        gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * mb * (double)n + 8.0 * (mb + n) * d);
-        hipLaunchKernelGGL(ep_mean_scale_kernel, dim3(mp / GP_NB), dim3(64 * EP_MS_CHUNKS), 0, s, Vt, mp, np, mb, n, w, ep->st(), fm);
-        GP_HIP(ctx, hipMemsetAsync(sumsq, 0, sizeof(double) * mp, s));
-        gpi_solve_rows_lower(ctx, Vt, mp, ep->L, np, ep->ldl, ep->dinv, sumsq, nullptr, nullptr, Lw);
-        hipLaunchKernelGGL(ep_prob_latent_kernel, g1(mb), dim3(256), 0, s, dprob + lo, dfmean ? dfmean + lo : nullptr,
-                           dfvar ? dfvar + lo : nullptr, fm, sumsq, kss, mb);
-    }
-    GP_LAUNCH_CHECK(ctx);
-    return GP_OK;
-}
-
-gp_status gp_ep_predict_rbf(gp_ep *ep, const double *Xs, int m, int ldxs, double *prob, double *fmean, double *fvar) {
-    if (!ep) return GP_EINVAL;
-    gp_ctx *ctx = ep->ctx;
-    GP_REQUIRE(ctx, ep->dX, "classifier was built from a Gram matrix");
-    GP_REQUIRE(ctx, Xs && prob && m >= 0 && ldxs >= m, "bad arguments");
-    GP_REQUIRE(ctx, ep->sweeps > 0, "classifier not trained: run gp_ep_sweep first");
-    if (m == 0) return GP_OK;
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    double *dXs, *dout;
-    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * ep->d, &dXs));
-    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)3 * m, &dout));
-    GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, ep->d));
-    GP_TRY(gp_ep_predict_rbf_dev(ep, dXs, m, m, 0, dout, fmean ? dout + m : nullptr, fvar ? dout + 2 * (size_t)m : nullptr));
-    GP_TRY(gpi_download_2d(ctx, prob, m, dout, m, m, 1));
-    if (fmean) GP_TRY(gpi_download_2d(ctx, fmean, m, dout + m, m, m, 1));
-    if (fvar) GP_TRY(gpi_download_2d(ctx, fvar, m, dout + 2 * (size_t)m, m, m, 1));
-    return GP_OK;
-}
-
-// EP log marginal likelihood at B hyper-parameter settings of the ARD-RBF kernel: what
-// MeshHyperParamsLogLikelihoodEvaluator.recEvaluate (gp/classification/MeshHyperParamsLogLikelihoodEvaluator.scala:26-40) asks of
-// MarginalLikelihoodEvaluator.logLikelihoodWithoutGrad (MarginalLikelihoodEvaluator.scala:24-31) one setting at a time, returned by
-// setting index (the reference's map is mis-keyed).  Per setting: Gram on the device, EP sweeps until
-// AvgBasedStopCriterion(stop_eps) holds (EpParameterEstimator.scala:187-202; sweep 0 always runs; stop_eps < 0: exactly
-// max_sweeps sweeps), EP LML (strict: as compiled).  Settings are independent: a few run concurrently, each on its own context.
-static gp_status ep_eval_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *thetas, int B,
-                                 double stop_eps, int max_sweeps, int strict, double *lml, double *grad, int *sweeps, int *info);
-
-gp_status gp_ep_lml_rbf_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *thetas, int B,
-                                double stop_eps, int max_sweeps, int strict, double *lml, int *sweeps, int *info) {
-    return ep_eval_batched(ctx, X, n, d, ldx, y, thetas, B, stop_eps, max_sweeps, strict, lml, nullptr, sweeps, info);
-}
-
-// MarginalLikelihoodEvaluator.logLikelihood (gp/classification/MarginalLikelihoodEvaluator.scala:33-44) at B settings: EP log
-// marginal likelihood AND its gradient w.r.t. all d+2 hyper-parameters (:46-66), grad B x (d+2) row-major.
-gp_status gp_ep_lml_grad_rbf_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *thetas, int B,
-                                     double stop_eps, int max_sweeps, int strict, double *lml, double *grad, int *sweeps, int *info) {
-    if (!ctx) return GP_EINVAL;
-    GP_REQUIRE(ctx, grad, "null gradient");
-    return ep_eval_batched(ctx, X, n, d, ldx, y, thetas, B, stop_eps, max_sweeps, strict, lml, grad, sweeps, info);
-}
-
-// GradientHyperParamsOptimizer.optimizeHyperParams (gp/classification/HyperParamsOptimization.scala:31-55): maximise the EP log
-// marginal likelihood over all d+2 hyper-parameters with the gradient-based optimiser it is wired with -- BreezeLbfgsOptimizer
-// (optimization/Optimization.scala:30-63: L-BFGS m = history, maxIter, best-seen point).  Every objective evaluation is a full
-// EP run (Gram -> sweeps until AvgBasedStopCriterion(stop_eps) or max_sweeps -> LML + gradient); the trial steps of one line
-// search are independent EP problems and run concurrently on the context's helper contexts.
-gp_status gp_ep_optimize_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *theta0, double stop_eps,
-                             int max_sweeps, int strict, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out,
-                             int *evals_out) {
-    if (!ctx) return GP_EINVAL;
-    GP_REQUIRE(ctx, X && y && theta0 && theta_out, "null pointer");
-    GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && ldx >= n && max_sweeps >= 1 && max_iter >= 0 && history >= 1, "bad arguments");
-    const int P = d + 2;
-    constexpr int NC = 3;   // trial steps per iteration (evaluated by ep_eval_batched: concurrently where that pays, GPCORE_EP_WORKERS)
-    auto evaluate = [&](const double *thetas, int count, double *f, double *g, int *bad) -> gp_status {
-        return ep_eval_batched(ctx, X, n, d, ldx, y, thetas, count, stop_eps, max_sweeps, strict, f, g, nullptr, bad);
-    };
-    return gpi_lbfgs_maximize(ctx, P, P, theta0, max_iter, history, NC, evaluate, theta_out, lml_out, iters_out, evals_out);
-}
-
-// B settings through lockstep sweeps.  G problems (GPCORE_EP_GROUP, default 12, capped by B and by free device memory: 5 np^2 doubles
-// each) live in one slab; a problem leaves when its stop criterion holds (AvgBasedStopCriterion as written, host side, per problem
-// per sweep) or at max_sweeps, gets its LML (and gradient) from the single-problem entry points on its view of the slab, and its
-// slot takes the next setting -- problems in one launch need not be at the same sweep.  Towards the end the slots above the last
-// active one drop out of the launches; a finished problem below it keeps sweeping (its results are already out).
-static gp_status ep_eval_lockstep(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *thetas, int B,
-                                  double stop_eps, int max_sweeps, int strict, double *lml, double *grad, int *sweeps, int *info) {
-    const int P = d + 2, np = gp_pad(n);
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    int G = 12;
-    if (const char *e = getenv("GPCORE_EP_GROUP")) G = atoi(e);
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const double per = 5.2 * 8.0 * (double)np * np;
-            G = std::min<long long>(G, (long long)(0.8 * (double)free_b / per));
-        }
-    }
-    G = std::max(1, std::min(G, B));
-    ep_slab sl;
-    GP_TRY(ep_slab_alloc(ctx, n, y, G, sl));
-    double *dX = nullptr;
-    gp_status st = gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)n * d, &dX);
-    if (st == GP_OK) st = gpi_upload_2d(ctx, dX, n, X, ldx, n, d);
-    if (st == GP_OK) gpk_centroid(ctx->stream, dX, n, d, n, gp_gram_center(ctx));      // one centre for every setting of the call
-    std::vector<int> slot_b(G, -1), slot_j(G, 0);
-    std::vector<double> cur((size_t)G * 2 * n, 0.0), old((size_t)G * 2 * n, 0.0), pull((size_t)G * 2 * np);
-    std::vector<int> hinfo(G, 0);
-    int next = 0, active = 0;
-    auto load = [&](int g) -> gp_status {      // the next setting into slot g: Gram on the device, sites zeroed, Sigma = K
-        slot_b[g] = -1;
-        if (next >= B) return GP_OK;
-        const int b = next++;
-        gp_ep *v = sl.ep[g];
-        gpk_gram_sym(ctx->stream, dX, n, d, n, thetas + (size_t)b * P, v->K, np, 1, 0.0, gp_gram_flag(ctx), gp_gram_center(ctx));
-        GP_TRY(ep_start(v));
-        slot_b[g] = b, slot_j[g] = 0;
-        std::fill(cur.begin() + (size_t)g * 2 * n, cur.begin() + (size_t)(g + 1) * 2 * n, 0.0);
-        ++active;
-        return GP_OK;
-    };
-    for (int g = 0; g < G && st == GP_OK; ++g) st = load(g);
-    while (st == GP_OK && active > 0) {
-        int count = 0;
-        for (int g = 0; g < G; ++g) if (slot_b[g] >= 0) count = g + 1;
-        st = ep_sweep_lockstep(sl, count);
-        if (st != GP_OK) break;
-        // tau | nu of every problem (the first 2 np doubles of its vector block) and the failing-pivot words, after ONE synchronisation
-        hipError_t e = hipMemcpy2DAsync(pull.data(), sizeof(double) * 2 * np, sl.ep[0]->vec, sizeof(double) * sl.sVec(), sizeof(double) * 2 * np, count,
-                                        hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), sl.info, sizeof(int) * count, hipMemcpyDeviceToHost, ctx->stream);
-        int ferr = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&ferr, sl.ep[0]->flags + np / GP_NB, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { GP_SET_ERR(ctx, "EP lockstep batch: %s", hipGetErrorString(e)); st = GP_EHIP; break; }
-        if (ferr) { GP_SET_ERR(ctx, "EP lockstep sweep: a device flag of the fused chain did not arrive within its bound (problem %d)", ferr - 1); st = GP_EHIP; break; }
-        for (int g = 0; g < count && st == GP_OK; ++g) {
-            const int b = slot_b[g];
-            if (b < 0) continue;
-            double *tn = cur.data() + (size_t)g * 2 * n, *to = old.data() + (size_t)g * 2 * n;
-            std::copy(tn, tn + 2 * n, to);
-            std::copy(pull.begin() + (size_t)g * 2 * np, pull.begin() + (size_t)g * 2 * np + n, tn);                 // tau
-            std::copy(pull.begin() + (size_t)g * 2 * np + np, pull.begin() + (size_t)g * 2 * np + np + n, tn + n);   // nu
-            const int j = ++slot_j[g];
-            bool done = j >= max_sweeps, bad = hinfo[g] != 0;
-            if (!done && !bad && stop_eps >= 0.0) {   // avgBetweenSiteParams :195-202: (sum / 2) * n, precedence as written
-                double sum = 0.0;
-                for (int i = 0; i < n; ++i) sum = sum + (tn[n + i] - to[n + i]) + (tn[i] - to[i]);
-                done = std::fabs(sum / 2 * n) < stop_eps;
-            }
-            if (!done && !bad) continue;
-            gp_ep *v = sl.ep[g];
-            if (bad) {
-                lml[b] = NAN;
-                if (grad) for (int q = 0; q < P; ++q) grad[(size_t)b * P + q] = NAN;
-                if (info) info[b] = hinfo[g];
-            } else {
-                st = gp_ep_lml(v, strict, lml + b);
-                if (st == GP_OK && grad) st = ep_lml_grad_dev(v, dX, d, thetas + (size_t)b * P, strict, grad + (size_t)b * P);
-                if (info) info[b] = 0;
-            }
-            if (sweeps) sweeps[b] = j;
-            --active;
-            if (st == GP_OK) st = load(g);
-            if (st == GP_OK && slot_b[g] < 0 && bad) st = ep_start(v);     // a failed problem that stays in the launches: back to a benign state
-        }
-    }
-    ep_slab_free(sl);
-    return st;
-}
-
-static gp_status ep_eval_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const int32_t *y, const double *thetas, int B,
-                                 double stop_eps, int max_sweeps, int strict, double *lml, double *grad, int *sweeps, int *info) {
-    if (!ctx) return GP_EINVAL;
-    GP_REQUIRE(ctx, X && y && thetas && lml, "null pointer");
-    GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && ldx >= n && B >= 0 && max_sweeps >= 1, "bad dimensions");
-    if (B == 0) return GP_OK;
-    const int P = d + 2;
-    {   // lockstep batch (ep_sweep_lockstep) whenever there are two settings and two site blocks; GPCORE_EP_LOCKSTEP = 0 selects the
-        // one-setting-at-a-time path below.  12 settings x 10 sweeps, aggregate sweeps/s one at a time -> lockstep (profiles/r03_m_ep_mesh_perf.log,
-        // r03_k_ep_mesh_perf2.log): n = 512 1778 -> 12110, n = 1024 831 -> 6081, n = 1536 570 -> 3028, n = 2048 416 -> 1600, n = 4096 184 -> 244
-        // (44.7 TFLOP/s executed: bound by the batched GEMMs, kernel stats in profiles/r03_k_lockstep_kernel_stats.csv), n = 8192 28.9 -> 30.5
-        const char *e = getenv("GPCORE_EP_LOCKSTEP");
-        const bool lock = e ? atoi(e) != 0 : B >= 2;
-        if (lock && gp_pad(n) >= 2 * GP_NB)
-            return ep_eval_lockstep(ctx, X, n, d, ldx, y, thetas, B, stop_eps, max_sweeps, strict, lml, grad, sweeps, info);
-    }
-    // Concurrent EP problems, each on its own context: with the streamed refactorisation one run keeps four streams busy and a second
-    // one only gets in its way (12 settings x 10 sweeps, aggregate sweeps/s with 1 / 2 / 3 workers: n = 2048 397 / 171 / 184, n = 4096
-    // 177 / 69 / 80); the end-of-sweep form of the small problems still gains from a second run (n = 512 1270 / 1499 / 1061, n = 1024
-    // 641 / 827 / 383).  GPCORE_EP_WORKERS overrides.
-    int nw = gp_pad(n) > 1024 ? 1 : 2;
-    if (const char *e = getenv("GPCORE_EP_WORKERS")) nw = atoi(e);
-    nw = std::max(1, std::min(std::min(nw, 8), B));
-    std::vector<gp_ctx *> ctxs(nw, nullptr);
-    ctxs[0] = ctx;
-    for (int k = 1; k < nw; ++k) {
-        ctxs[k] = gpi_child_ctx(ctx, k - 1);
-        if (!ctxs[k]) { nw = k; break; }
-    }
-    std::vector<gp_status> sts(nw, GP_OK);
-    std::atomic<int> next{0};
-    auto run = [&](int k) {
-        gp_ctx *c = ctxs[k];
-        gp_ep *ep = nullptr;
-        gp_status st = ep_alloc(c, n, y, &ep);
-        double *dX = nullptr;
-        if (st == GP_OK) st = gpi_ws_get(c, WS_A, sizeof(double) * (size_t)n * d, &dX);
-        if (st == GP_OK) st = gpi_upload_2d(c, dX, n, X, ldx, n, d);
-        if (st == GP_OK) gpk_centroid(c->stream, dX, n, d, n, gp_gram_center(c));
-        std::vector<double> tau(n), nu(n), tau_old(n), nu_old(n);
-        while (st == GP_OK) {
-            const int b = next.fetch_add(1);
-            if (b >= B) break;
-            gpk_gram_sym(c->stream, dX, n, d, n, thetas + (size_t)b * P, ep->K, ep->np, 1, 0.0, gp_gram_flag(c), gp_gram_center(c));
-            st = ep_start(ep);
-            int j = 0, h = 0;
-            std::fill(tau.begin(), tau.end(), 0.0);
-            std::fill(nu.begin(), nu.end(), 0.0);
-            gp_status es = GP_OK;
-            while (st == GP_OK && es == GP_OK) {
-                tau_old = tau, nu_old = nu;
-                es = gp_ep_sweep(ep, 1, tau.data(), nu.data(), &h);
-                if (es != GP_OK) break;
-                ++j;
-                if (j >= max_sweeps) break;
-                if (stop_eps >= 0.0) {   // avgBetweenSiteParams :195-202: (sum / 2) * n, precedence as written
-                    double sum = 0.0;
-                    for (int i = 0; i < n; ++i) sum = sum + (nu[i] - nu_old[i]) + (tau[i] - tau_old[i]);
-                    if (std::fabs(sum / 2 * n) < stop_eps) break;
-                }
-            }
-            if (es == GP_ENOTPD) {
-                lml[b] = NAN;
-                if (grad) for (int q = 0; q < P; ++q) grad[(size_t)b * P + q] = NAN;
-                if (info) info[b] = h;
-            } else if (es != GP_OK) {
-                st = es;
-            } else if (st == GP_OK) {
-                st = gp_ep_lml(ep, strict, lml + b);
-                if (st == GP_OK && grad) st = ep_lml_grad_dev(ep, dX, d, thetas + (size_t)b * P, strict, grad + (size_t)b * P);
-                if (info) info[b] = 0;
-            }
-            if (sweeps) sweeps[b] = j;
-        }
-        if (ep) gp_ep_destroy(ep);
-        sts[k] = st;
-    };
-    std::vector<std::thread> threads;
-    for (int k = 1; k < nw; ++k) threads.emplace_back(run, k);
-    run(0);
-    for (auto &t : threads) t.join();
-    for (int k = 0; k < nw; ++k)
-        if (sts[k] != GP_OK) {
-            if (k > 0) GP_SET_ERR(ctx, "%s", ctxs[k]->err);
-            return sts[k];
-        }
-    return GP_OK;
 }
 
 #ifdef EP_STAMPS

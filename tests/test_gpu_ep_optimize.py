@@ -113,7 +113,7 @@ def test_gradient_hyper_params_optimizer_mirror(ctx):
     assert after >= before
 
 
-# ---- lockstep batch over settings (ep_sweep_lockstep): MeshHyperParamsLogLikelihoodEvaluator.scala:26-40 at size --------------------
+# ---- lockstep batch over settings (ep_slab_sweep -> ep_sweep_once): MeshHyperParamsLogLikelihoodEvaluator.scala:26-40 at size --------------------
 @pytest.mark.parametrize("strict", [True, False])
 def test_ep_lockstep_batch_vs_oracle_small(ctx, monkeypatch, strict):
     """The lockstep form forced at a size the oracle runs to convergence in seconds: 7 settings through a slab of 3 slots (slots are
@@ -140,6 +140,31 @@ def test_ep_lockstep_batch_vs_oracle_small(ctx, monkeypatch, strict):
     monkeypatch.setenv("GPCORE_EP_PIPELINE", "1")
     monkeypatch.setenv("GPCORE_EP_WORKERS", "1")
     l1, g1, s1, _ = ctx.ep_lml_grad_rbf_batched(p["X"], y, thetas, stop_eps=0.01, max_sweeps=30, strict=strict)
+    assert np.array_equal(l1, lml) and np.array_equal(g1, grad) and np.array_equal(s1, sweeps)
+
+
+@pytest.mark.parametrize("n", [129, 256])
+def test_ep_lockstep_smallest_and_ragged_batch(ctx, monkeypatch, n):
+    """np = 256, the smallest size at which the lockstep form engages: n = 129 leaves ONE live site in the second block, n = 256 has no
+    padding.  Three settings through a slab of two slots (one slot is refilled), three sweeps each: LML and gradient against the oracle,
+    then bit for bit against one setting at a time in the same form of the sweep."""
+    monkeypatch.setenv("GPCORE_EP_GROUP", "2")
+    p, y = _ep_problem(n, seed=67)
+    rng = np.random.default_rng(4)
+    thetas = p["theta"][None, :] * rng.uniform(0.7, 1.4, size=(3, 5))
+    lml, grad, sweeps, info = ctx.ep_lml_grad_rbf_batched(p["X"], y, thetas, stop_eps=-1.0, max_sweeps=3, strict=False)
+    assert np.all(info == 0) and list(sweeps) == [3] * 3
+    for b in range(3):
+        K = orc.gram_sym(p["X"], thetas[b])
+        o = orc.ep_estimate(K, y, 3)
+        ol = orc.ep_lml(o, y, False)
+        og = orc.ep_lml_grad(p["X"], thetas[b], K, o["L"], o["tau"], o["nu"], strict=False)
+        assert abs(lml[b] - ol) <= 1e-8 * abs(ol), b
+        assert np.max(np.abs(grad[b] - og)) <= TOL_GRAD * np.max(np.abs(og)), b
+    monkeypatch.setenv("GPCORE_EP_LOCKSTEP", "0")
+    monkeypatch.setenv("GPCORE_EP_PIPELINE", "1")
+    monkeypatch.setenv("GPCORE_EP_WORKERS", "1")
+    l1, g1, s1, _ = ctx.ep_lml_grad_rbf_batched(p["X"], y, thetas, stop_eps=-1.0, max_sweeps=3, strict=False)
     assert np.array_equal(l1, lml) and np.array_equal(g1, grad) and np.array_equal(s1, sweeps)
 
 

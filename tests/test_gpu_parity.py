@@ -539,6 +539,37 @@ def test_ep_fused_chain_equals_block_and_link_kernels(ctx, monkeypatch):
     assert np.array_equal(got["1"][0], got["0"][0]) and np.array_equal(got["1"][1], got["0"][1])
 
 
+_EP_FORMS_CASE = []      # (K, y, oracle state) of the problem below, computed once for all forms
+
+
+@pytest.mark.parametrize("env", [
+    dict(OVERLAP="0"),
+    dict(PIPELINE="1", URGENT="0"),
+    dict(PIPELINE="1", FAR="0"),
+    dict(PIPELINE="1", FUSED="0", LINK="0"),
+    dict(PIPELINE="0", FUSED="1"),
+], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
+def test_ep_sweep_forms_no_default_selects_vs_oracle(ctx, monkeypatch, env):
+    """The forms of the sweep that no default and no other test reaches: everything on one stream, the streamed refactorisation without
+    urgent tiles / without the far split / with block kernel + two-launch link, and the fused chain with the end-of-sweep
+    refactorisation.  n = 300 (np = 384): three site blocks, so the waits of block b >= 2 and the urgent counter are in play.  Two
+    sweeps, the whole state against the oracle's literal loop."""
+    from gp_algos_amd import _lib as L
+    from gp_algos_amd.core import EpClassifierState
+    if not _EP_FORMS_CASE:
+        _, K, y = _ep_problem(300, seed=61)
+        _EP_FORMS_CASE.append((K, y, orc.ep_estimate(K, y, 2)))
+    K, y, o = _EP_FORMS_CASE[0]
+    for name, val in env.items():
+        monkeypatch.setenv("GPCORE_EP_" + name, val)
+    ep = EpClassifierState(ctx, K, y)
+    tau, nu = ep.sweep(2)
+    got = dict(tau=tau, nu=nu, mu=ep.get(L.GP_EP_GET_MU), Sigma=ep.get(L.GP_EP_GET_SIGMA))
+    ep.close()
+    for key, val in got.items():
+        assert np.max(np.abs(val - o[key])) <= TOL_EP * np.max(np.abs(o[key])), key
+
+
 def test_ep_50_sweeps_drift_vs_oracle(ctx):
     """Fifty sweeps: rounding differences between the blocked form and the literal loop must not accumulate from sweep to sweep."""
     from gp_algos_amd import _lib as L

@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="hipcc not available")
 @pytest.mark.parametrize("src", sorted(glob.glob(os.path.join(ROOT, "gp_algos_amd", "csrc", "kernels_*.hip")) +
-                                       glob.glob(os.path.join(ROOT, "gp_algos_amd", "csrc", "gpcore_ep.hip"))),
+                                       glob.glob(os.path.join(ROOT, "gp_algos_amd", "csrc", "gpcore_ep*.hip"))),
                          ids=os.path.basename)
 def test_no_kernel_uses_scratch(src, tmp_path):
     out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-Rpass-analysis=kernel-resource-usage",
