@@ -89,7 +89,14 @@ SIGNATURES = {
     "gp_fit_co2": (_i, [_vp, _dp, _i, _dp, _dp, _d, C.POINTER(_vp), _ip]),
     "gp_lml_grad_co2_batched": (_i, [_vp, _dp, _i, _dp, _dp, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_co2": (_i, [_vp, _dp, _i, _dp, _dp, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
-    "gp_small_fit": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
+    "gp_gram_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _i]),
+    "gp_gram_matern_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, _i, _vp, _i, _i]),
+    "gp_cross_gram_matern": (_i, [_vp, _dp, _i, _i, _dp, _i, _i, _i, _dp, _i, _dp, _i]),
+    "gp_fit_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _d, C.POINTER(_vp), _ip]),
+    "gp_fit_matern_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _i, _d, C.POINTER(_vp), _ip]),
+    "gp_lml_grad_matern_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
+    "gp_optimize_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
+    "gp_small_fit":(_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
     "gp_small_from_factors": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_vp)]),
     "gp_small_destroy": (None, [_vp]),
     "gp_small_size": (_i, [_vp, _ip, _ip, _ip]),

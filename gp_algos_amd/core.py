@@ -208,6 +208,57 @@ class Context:
                                              L.dptr(out), L.dptr(lml), C.byref(its), C.byref(evs)))
         return out, float(lml[0]), its.value, evs.value
 
+    # -- ARD Matern kernels, nu2 = 2 nu: 3 (nu = 3/2) or 5 (nu = 5/2); theta = (sf, l_1..l_d, sn) -------------------------------------
+    def gram_matern(self, X, theta, nu2, full=True, xs=None, out=None):
+        """Gram (xs None: full symmetric, or the lower triangle written into `out`) / cross-Gram (xs given: len(xs) x n)."""
+        X, theta = L.f64(X), L.f64(theta)
+        n, d = X.shape
+        if theta.size != d + 2:
+            raise ValueError("%d does not equal to %d" % (theta.size, d + 2))
+        if xs is not None:
+            xs = L.f64(xs)
+            m = xs.shape[0]
+            if xs.shape[1] != d:
+                raise ValueError("dimension mismatch")
+            Ks = np.zeros((m, n), order="F")
+            self.check(self._lib.gp_cross_gram_matern(self.h, L.dptr(xs), m, max(m, 1), L.dptr(X), n, max(n, 1), d, L.dptr(theta), int(nu2),
+                                                      L.dptr(Ks), max(m, 1)))
+            return Ks
+        K = np.zeros((n, n), order="F") if out is None else out
+        self.check(self._lib.gp_gram_matern(self.h, L.dptr(X), n, d, max(n, 1), L.dptr(theta), int(nu2), L.dptr(K), max(n, 1),
+                                            L.GP_FULL if full else L.GP_LOWER))
+        return K
+
+    def lml_grad_matern_batched(self, X, y, thetas, nu2, nparams=None, sigma_noise=None):
+        """gp_lml_grad_matern_batched: (lml[B], grad[B, nparams], info[B])."""
+        X, y = L.f64(X), L.f64(y)
+        n, d = X.shape
+        thetas = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+        B, P = thetas.shape
+        if P != d + 2 or y.size != n:
+            raise ValueError("dimension mismatch")
+        nparams = P if nparams is None else int(nparams)
+        lml, grad, info = np.zeros(B), np.zeros((B, max(nparams, 1))), np.zeros(B, dtype=np.int32)
+        sn = float("nan") if sigma_noise is None else float(sigma_noise)
+        self.check(self._lib.gp_lml_grad_matern_batched(self.h, L.dptr(X), n, d, n, L.dptr(y), L.dptr(thetas), B, nparams, int(nu2), sn,
+                                                        L.dptr(lml), L.dptr(grad), info.ctypes.data_as(C.POINTER(C.c_int))))
+        return lml, grad[:, :nparams], info
+
+    def optimize_matern(self, X, y, theta0, nu2, nparams=None, sigma_noise=None, max_iter=20, history=4):
+        """gp_optimize_matern: (theta*, LML(theta*), iterations, evaluations)."""
+        X, y = L.f64(X), L.f64(y)
+        n, d = X.shape
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+        if theta0.size != d + 2 or y.size != n:
+            raise ValueError("dimension mismatch")
+        nparams = d + 2 if nparams is None else int(nparams)
+        out, lml = np.zeros(d + 2), np.zeros(1)
+        its, evs = C.c_int(0), C.c_int(0)
+        sn = float("nan") if sigma_noise is None else float(sigma_noise)
+        self.check(self._lib.gp_optimize_matern(self.h, L.dptr(X), n, d, n, L.dptr(y), L.dptr(theta0), nparams, int(nu2), sn, int(max_iter),
+                                                int(history), L.dptr(out), L.dptr(lml), C.byref(its), C.byref(evs)))
+        return out, float(lml[0]), its.value, evs.value
+
     def posterior_from_factor(self, X, theta, Lm, alpha, Xs, full_cov=False, want_v=False):
         """gp_posterior_from_factor (GpPredictor.computePosterior with the ARD-RBF kernel): (mean, var, cov|None, V|None)."""
         X, theta, Lm, alpha, Xs = L.f64(X), L.f64(theta), L.f64(Lm), L.f64(alpha), L.f64(Xs)
@@ -345,6 +396,15 @@ class RegressionModel:
             if theta.size != 11:
                 raise ValueError("Co2Kernel takes 11 hyper-parameters")
             st = lib.gp_fit_co2(ctx.h, L.dptr(x), self.n, L.dptr(y), L.dptr(theta), sn, C.byref(h), C.byref(info))
+        elif kernel in ("matern32", "matern52"):   # gp_fit_matern: ARD Matern 3/2 / 5/2, theta = (sf, l_1..l_d, sn)
+            X, theta = L.f64(X), L.f64(theta)
+            self.n, self.d = X.shape
+            if y.size != self.n:
+                raise ValueError("Number of objects in training data matrix should be equal to targets vector length")
+            if theta.size != self.d + 2:
+                raise ValueError("%d does not equal to %d" % (theta.size, self.d + 2))
+            st = lib.gp_fit_matern(ctx.h, L.dptr(X), self.n, self.d, self.n, L.dptr(y), L.dptr(theta), 3 if kernel == "matern32" else 5, sn,
+                                   C.byref(h), C.byref(info))
         else:
             X, theta = L.f64(X), L.f64(theta)
             self.n, self.d = X.shape

@@ -495,6 +495,7 @@ gp_status gp_model_refit_dev(gp_model *m, const double *theta, double sigma_nois
     m->sigma_noise = sigma_noise;
     gp_prof_begin(ctx, GP_PROF_GRAM);
     if (m->kind == 1) gpk_co2_gram(ctx->stream, m->dX, m->n, m->dX, m->n, theta, 0, m->dL, m->ldl, 1, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise);
+    else if (m->kind >= 2) gpk_matern_gram_sym(ctx->stream, m->dX, m->n, m->d, m->ldx, theta, 2 * m->kind - 1, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
     else gpk_gram_sym(ctx->stream, m->dX, m->n, m->d, m->ldx, theta, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m->n * (m->n + 1.0) / 2.0 + 8.0 * m->n * m->d);
     model_factor(m);
@@ -673,6 +674,7 @@ static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs,
     }
     gp_prof_begin(ctx, GP_PROF_GRAM);
     if (mdl->kind == 1) gpk_co2_gram(s, dXs, m, mdl->dX, n, mdl->theta.data(), 0, Vt, mp, 0, 1, 0.0);
+    else if (mdl->kind >= 2) gpk_matern_gram_cross(s, dXs, m, ldxs, mdl->dX, n, mdl->ldx, mdl->d, mdl->theta.data(), 2 * mdl->kind - 1, Vt, mp, gp_gram_flag(ctx), mdl->dcen);
     else gpk_gram_cross(s, dXs, m, ldxs, mdl->dX, n, mdl->ldx, mdl->d, mdl->theta.data(), Vt, mp, gp_gram_flag(ctx), mdl->dcen);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m * (double)n + 8.0 * (m + n) * mdl->d);
     // sumsq and the mean accumulate inside the row-panel solves: var = kss - |v|^2, mean = v . (L^-1 y)  (= K* alpha)
@@ -754,6 +756,7 @@ gp_status gp_predict(gp_model *mdl, const double *Xs, int m, int ldxs, double *m
         double *dC;
         GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)mp * mp, &dC));
         if (mdl->kind == 1) gpk_co2_gram(ctx->stream, dXs, m, dXs, m, mdl->theta.data(), 0, dC, mp, 1, 1, 0.0);
+        else if (mdl->kind >= 2) gpk_matern_gram_sym(ctx->stream, dXs, m, d, m, mdl->theta.data(), 2 * mdl->kind - 1, dC, mp, 1, 0.0, gp_gram_flag(ctx));
         else gpk_gram_sym(ctx->stream, dXs, m, d, m, mdl->theta.data(), dC, mp, 1, 0.0, gp_gram_flag(ctx));
         gpk_pad_identity(ctx->stream, dC, m, mp, mp);
         gp_prof_begin(ctx, GP_PROF_SYRK);

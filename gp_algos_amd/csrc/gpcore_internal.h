@@ -55,7 +55,8 @@ struct gp_model {
     int n = 0, d = 0, np = 0;        // np = padded n
     int ldl = 0;                     // leading dimension of dL = np + GP_NB: one extra row strip carries y^T through the factorisation
     bool has_x = false;              // false for gp_fit_from_gram
-    int kind = 0;                    // kernel the model rebuilds Gram matrices with: 0 = ARD-RBF (theta = d + 2), 1 = Co2Kernel (d = 1, theta = 11)
+    int kind = 0;                    // kernel the model rebuilds Gram matrices with: 0 = ARD-RBF (theta = d + 2), 1 = Co2Kernel (d = 1, theta = 11),
+                                     // 2 / 3 = ARD Matern 3/2 / 5/2 (theta = d + 2; nu2 = 2 kind - 1)
     double *dX = nullptr;            // n x d, ld = ldx
     int ldx = 0;                     // leading dimension of dX: n as fitted, the padded size once gp_model_append_dev has made room
     double *dcen = nullptr;          // d: centroid of the rows of dX (centre of the matrix-core Gram forms), set with dX
@@ -130,6 +131,16 @@ void gpk_gram_cross(hipStream_t s, const double *Xs, int m, int ldxs, const doub
 inline int *gp_gram_flag(gp_ctx *ctx) { return ctx->d_info + 4; }     // d_info holds 8 ints: [0..3] factorisation status, [4] the Gram scan's flag
 // per-call centre of a Gram build whose inputs no model owns (GP_DMAX doubles behind the 8 ints of d_info, used in stream order)
 inline double *gp_gram_center(gp_ctx *ctx) { return reinterpret_cast<double *>(ctx->d_info + 8); }
+int gpk_gram_epoch();     // a value no earlier Gram call of this process wrote into a scan flag
+// ARD Matern, nu2 = 2 nu in {3, 5} (kernels_matern.hip); theta, far_flag and center as for gpk_gram_sym / gpk_gram_cross
+void gpk_matern_gram_sym(hipStream_t s, const double *X, int n, int d, int ldx, const double *theta, int nu2, double *K, int ldk, int full, double extra_diag,
+                         int *far_flag, const double *center = nullptr);
+void gpk_matern_gram_cross(hipStream_t s, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta, int nu2, double *Ks,
+                           int ldks, int *far_flag, const double *center = nullptr);
+// out[0..d+1] = 1/2 tr((alpha alpha^T - Kinv) dK/dtheta_p), one pass (lower triangle of Kinv read); partials: gpk_matern_trace_partials_size(d) doubles
+void gpk_matern_lml_grad_traces(hipStream_t s, const double *X, int n, int d, int ldx, const double *theta, int nu2, const double *alpha, const double *Kinv,
+                                int ldk, double *partials, double *out);
+int gpk_matern_trace_partials_size(int d);
 // Co2Kernel (gp/regression/Co2Prediction.scala:29-137), 1-D inputs, theta = hp1..hp11 on the host; pos = 0: kernel, 1..11: derivative
 void gpk_co2_gram(hipStream_t s, const double *xr, int nr, const double *xc, int nc, const double *theta, int pos, double *K, int ldk, int sym,
                   int full, double extra);

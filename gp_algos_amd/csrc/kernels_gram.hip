@@ -522,6 +522,7 @@ static int next_epoch() {
     int v = e.fetch_add(1) + 1;
     return v <= 0 ? (e = 1, 1) : v;     // wraps after 2^31 calls
 }
+int gpk_gram_epoch() { return next_epoch(); }     // the Matern builders (kernels_matern.hip) share the scan's flag, so they share its epochs
 
 template <int MODE>
 static void launch_unit(hipStream_t s, const double *Xr, int nr, int ldxr, const double *Xc, int nc, int ldxc, int d, const GramParams &p,

@@ -292,6 +292,30 @@ gp_status gp_lml_grad_co2_batched(gp_ctx *ctx, const double *x, int n, const dou
 /* GpPredictor.obtainOptimalHyperParams (:126-142) with Co2Kernel: L-BFGS (m = history, maxIter = max_iter, best-seen point). */
 gp_status gp_optimize_co2(gp_ctx *ctx, const double *x, int n, const double *y, const double *theta0, int nparams, double sigma_noise, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out, int *evals_out);
 
+/* ---- ARD Matern kernels, nu = 3/2 and 5/2 ------------------------------------------------------ */
+/* theta = (sf, l_1..l_d, sn) as for the ARD-RBF kernel (P = d + 2); nu2 = 2 nu: 3 or 5, anything else GP_EINVAL, as are d outside 1..64
+ * and bad leading dimensions.  With z_k = (x_k - y_k) / l_k, r^2 = sum_k z_k^2, a = sqrt(nu2) r:
+ *     nu = 3/2:  k = sf^2 (1 + a) exp(-a)                    nu = 5/2:  k = sf^2 (1 + a + a^2 / 3) exp(-a)
+ * and the diagonal of a symmetric Gram matrix is sf*sf + sn*sn (+ sigma_noise) exactly.  Derivatives (none divides by r):
+ *     dK/dsf = 2 K0 / sf  (K0: K without the noise term),    dK/dsn = 2 sn I,
+ *     dK/dl_k = sf^2 h(a) z_k^2 / l_k   with  h = 3 exp(-a)  (3/2)   resp.  h = 5/3 (1 + a) exp(-a)  (5/2).
+ * Same contracts as the *_rbf entry points of the same names. */
+gp_status gp_gram_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *theta, int nu2, double *K, int ldk, int uplo);
+gp_status gp_gram_matern_dev(gp_ctx *ctx, const double *dX, int n, int d, int ldx, const double *theta, int nu2, double *dK, int ldk, int uplo);
+gp_status gp_cross_gram_matern(gp_ctx *ctx, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta, int nu2, double *Ks, int ldks);
+/* The returned model works with gp_model_refit_dev (theta = d + 2 values), gp_model_status, gp_model_get, gp_predict (mean, variance,
+ * covariance; prior variance sf^2 + sn^2), gp_predict_dev and gp_dist_predict.  gp_predict_grad*, gp_model_ucb, gp_model_maximize_ucb and
+ * gp_model_append* refuse it with GP_EINVAL (ARD-RBF models only) and leave it untouched. */
+gp_status gp_fit_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta, int nu2, double sigma_noise, gp_model **out, int *info);
+gp_status gp_fit_matern_dev(gp_ctx *ctx, const double *dX, int n, int d, int ldx, const double *dy, const double *theta, int nu2, double sigma_noise, gp_model **out, int *info);
+/* Log marginal likelihood and its gradient g_p = 1/2 tr((alpha alpha^T - K^-1) dK/dtheta_p) at B settings (thetas B x (d + 2) row-major),
+ * one setting at a time through a resident model; all components come from ONE pass over alpha alpha^T - K^-1 (no derivative matrix is
+ * built).  grad is B x nparams: the first nparams <= d + 2 components.  A setting whose matrix is not positive definite gets NaN and its
+ * pivot in info[b]; the batch goes on. */
+gp_status gp_lml_grad_matern_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *thetas, int B, int nparams, int nu2, double sigma_noise, double *lml, double *grad, int *info);
+/* L-BFGS on the first nparams hyper-parameters (m = history, maxIter = max_iter, best-seen point), as gp_optimize_rbf. */
+gp_status gp_optimize_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int nu2, double sigma_noise, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out, int *evals_out);
+
 /* ---- batched small-n posteriors: GP-UCB and GP-UKF --------------------------------------------- */
 /* The heaviest callers of GpPredictor.computePosterior (gp/regression/GpPredictor.scala:45-58) ask for ONE test point per call
  * against a few hundred training points: GPOptimizer.maximizeUCB (gp/optimization/GPOptimizer.scala:82-109) inside L-BFGS, and
