@@ -1,7 +1,7 @@
 """gp_algos_amd -- MI355X-native Gaussian-process hot path behind the reference's API names.
 
 Layout mirrors the reference packages (astroHaoPeng/gp_algos, src/main/scala):
-    utils.kernel_requisites   <- utils/KernelRequisites.scala   (GaussianRbfParams, GaussianRbfKernel, KernelFunc)
+    utils.kernel_requisites   <- utils/KernelRequisites.scala   (GaussianRbfParams, GaussianRbfKernel, KernelFunc; MaternKernel)
     utils.matrix_utils        <- utils/MatrixUtils.scala        (buildKernelMatrix, forwardSolve, backSolve, invTriangular)
     utils.stats_utils         <- utils/StatsUtils.scala         (pnorm, dnorm, GaussianDistribution)
     gp.regression.gp_predictor        <- gp/regression/GpPredictor.scala

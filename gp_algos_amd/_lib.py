@@ -98,6 +98,8 @@ SIGNATURES = {
     "gp_optimize_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
     "gp_small_fit":(_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
     "gp_small_from_factors": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_vp)]),
+    "gp_small_fit_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _i, _d, _i, C.POINTER(_vp), _ip]),
+    "gp_small_from_factors_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, _i, C.POINTER(_vp)]),
     "gp_small_destroy": (None, [_vp]),
     "gp_small_size": (_i, [_vp, _ip, _ip, _ip]),
     "gp_small_get": (_i, [_vp, _i, _i, _dp, _i]),

@@ -542,9 +542,14 @@ class RegressionModel:
 
 
 class SmallModelBatch:
-    """gp_small_*: G small GP models over ONE set of training inputs, resident with L^-1 (GP-UCB / GP-UKF workloads)."""
+    """gp_small_*: G small GP models over ONE set of training inputs, resident with L^-1 (GP-UCB / GP-UKF workloads).
+    kernel = "rbf" (ARD-RBF, the default), "matern32" or "matern52" (gp_small_fit_matern / gp_small_from_factors_matern); every
+    method works on either kind."""
 
-    def __init__(self, ctx, X, thetas, Y=None, Ls=None, alphas=None, sigma_noise=None, capacity=0):
+    def __init__(self, ctx, X, thetas, Y=None, Ls=None, alphas=None, sigma_noise=None, capacity=0, kernel="rbf"):
+        if kernel not in ("rbf", "matern32", "matern52"):
+            raise ValueError("kernel must be 'rbf', 'matern32' or 'matern52'")
+        nu2 = {"rbf": 0, "matern32": 3, "matern52": 5}[kernel]
         self.ctx = ctx
         X = L.f64(X)
         self.n0, self.d = X.shape
@@ -559,13 +564,21 @@ class SmallModelBatch:
             if Y.shape[1] != self.G:
                 raise ValueError("one target column per model")
             sn = float("nan") if sigma_noise is None else float(sigma_noise)
-            st = ctx._lib.gp_small_fit(ctx.h, L.dptr(X), n, self.d, n, L.dptr(Y), n, self.G, L.dptr(thetas), sn, int(capacity), C.byref(h), C.byref(info))
+            if nu2:
+                st = ctx._lib.gp_small_fit_matern(ctx.h, L.dptr(X), n, self.d, n, L.dptr(Y), n, self.G, L.dptr(thetas), nu2, sn, int(capacity),
+                                                  C.byref(h), C.byref(info))
+            else:
+                st = ctx._lib.gp_small_fit(ctx.h, L.dptr(X), n, self.d, n, L.dptr(Y), n, self.G, L.dptr(thetas), sn, int(capacity), C.byref(h), C.byref(info))
         else:
             Ls = np.asfortranarray(np.concatenate([L.f64(a) for a in Ls], axis=1))       # n x (G n): model g at columns [g n, (g+1) n)
             alphas = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float64) for a in alphas]))
             if Ls.shape != (n, self.G * n) or alphas.shape != (self.G, n):
                 raise ValueError("dimension mismatch")
-            st = ctx._lib.gp_small_from_factors(ctx.h, L.dptr(X), n, self.d, n, L.dptr(thetas), self.G, L.dptr(Ls), n, L.dptr(alphas), int(capacity), C.byref(h))
+            if nu2:
+                st = ctx._lib.gp_small_from_factors_matern(ctx.h, L.dptr(X), n, self.d, n, L.dptr(thetas), self.G, L.dptr(Ls), n, L.dptr(alphas), nu2,
+                                                           int(capacity), C.byref(h))
+            else:
+                st = ctx._lib.gp_small_from_factors(ctx.h, L.dptr(X), n, self.d, n, L.dptr(thetas), self.G, L.dptr(Ls), n, L.dptr(alphas), int(capacity), C.byref(h))
         ctx.check(st, info.value)
         self.h = h
 

@@ -9,6 +9,17 @@
 // and for the UCB objective its input gradient through GaussianRbfKernel.gradient (utils/KernelRequisites.scala:95-107).
 // A point is APPENDED by a rank-1 extension of L, L^-1 and alpha (O(n^2)) instead of the reference's O(n^3) refit per
 // iteration (GPOptimizer.scala:51).
+//
+// The kernels are instantiated on NU2 = 2 nu in {0 (ARD-RBF, the reference's kernel), 3, 5 (ARD Matern 3/2 and 5/2, kernels_matern.hip)}.
+// With z_k = (x*_k - X_jk) / l_k, r^2 = sum_k z_k^2, a = sqrt(NU2 r^2):
+//   nu = 3/2:  k = sf^2 (1 + a) exp(-a)               h = 3 exp(-a)
+//   nu = 5/2:  k = sf^2 (1 + a + a^2 / 3) exp(-a)     h = 5/3 (1 + a) exp(-a)
+//   D(j, k) = d k(x*, X_j) / d x*_k = -sf^2 h_j (x*_k - X_jk) / l_k^2
+// Nothing divides by r, and a test point ON a training point gets D = 0 from the zero difference.  For nu = 5/2 that is the derivative
+// (the kernel is twice differentiable); for nu = 3/2 the kernel has a kink at r = 0 and 0 is the element of its subdifferential that
+// matern_trace_kernel's h = 3 exp(-a) already stands for in the length-scale derivative.
+// A handle carries its kind (0, 2, 3 as gp_model does) and every launch site dispatches on it; the NU2 = 0 instantiations are the
+// kernels as they were before the Matern ones existed, instruction for instruction.
 #include "gpcore_internal.h"
 
 #include <algorithm>
@@ -28,6 +39,7 @@ struct gp_small {
     double *dalpha_next = nullptr;   // G x cap: gp_small_append builds the extended alpha here and swaps it in only if EVERY model succeeded
     double *dtheta = nullptr;   // G x (d + 2)
     bool has_y = false;
+    int kind = 0;               // 0: ARD-RBF, 2: Matern 3/2, 3: Matern 5/2 (as gp_model)
     std::vector<double> thetas;
 };
 
@@ -58,24 +70,51 @@ __device__ __forceinline__ double rbf_pair(const double *xs, const double *X, in
     return th[0] * th[0] * exp(-0.5 * acc);
 }
 
+// The Matern pair in matern_pair_kernel's order (kernels_matern.hip): differences first, (diff l^-2) diff accumulated by fma -- nothing is
+// subtracted after a sum, so inputs far from the origin lose nothing -- then sqrt / polynomial / exp, times sf^2.  il2[k] = 1 / l_k^2
+// comes from LDS, divided once per workgroup (rbf_pair divides per pair and feature).  `gh` is the derivative factor sf^2 h, from the
+// exp(-a) that is in a register anyway; where it is not used it is dead code.
+template <int NU2>
+__device__ __forceinline__ double matern_pair(const double *xs, const double *il2, const double *X, int ldx, int j, int d, double sf2, double &gh) {
+    double r2 = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double diff = xs[k] - X[j + (size_t)k * ldx];
+        r2 = fma(diff * il2[k], diff, r2);
+    }
+    const double a = sqrt((double)NU2 * r2), e = exp(-a);
+    if (NU2 == 3) {
+        gh = sf2 * (3.0 * e);
+        return sf2 * ((1.0 + a) * e);
+    }
+    gh = sf2 * ((5.0 / 3.0) * ((1.0 + a) * e));
+    return sf2 * (fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0) * e);
+}
+
 // One workgroup per (test point, model).  UCB: also value = mean + kappa sqrt(var) and its gradient w.r.t. the test point.
 //   mean[g * m + i], var[g * m + i];  UCB (one model `g0`): value[i], grad[i * d + k]
-template <bool UCB>
+// LDS: ks | v | (UCB: w) | (UCB and Matern: hs = sf^2 h, what the gradient loop reads where RBF reads ks) | xs[64] | (Matern: il2[64]) | red
+template <bool UCB, int NU2>
 __global__ __launch_bounds__(SM_THREADS) void small_posterior_kernel(int n, int cap, int d, int g0, const double *__restrict__ X,
                                                                      const double *__restrict__ Linv, const double *__restrict__ alpha,
                                                                      const double *__restrict__ theta, const double *__restrict__ Xs, int m,
                                                                      int ldxs, double kappa, double *__restrict__ mean, double *__restrict__ var,
                                                                      double *__restrict__ grad) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *ks = sm, *v = sm + cap, *w = v + cap, *xs = w + (UCB ? cap : 0), *red = xs + 64;
+    double *ks = sm, *v = sm + cap, *w = v + cap, *hs = w + (UCB ? cap : 0), *xs = hs + (UCB && NU2 ? cap : 0), *il2 = xs + 64, *red = il2 + (NU2 ? 64 : 0);
     const int tid = threadIdx.x, i = blockIdx.x, g = UCB ? g0 : blockIdx.y;
     const double *th = theta + (size_t)g * (d + 2), *Li = Linv + (size_t)g * cap * cap, *al = alpha + (size_t)g * cap;
-    if (tid < d) xs[tid] = Xs[i + (size_t)tid * ldxs];
+    if (tid < d) {
+        xs[tid] = Xs[i + (size_t)tid * ldxs];
+        if (NU2) il2[tid] = 1.0 / (th[1 + tid] * th[1 + tid]);
+    }
     __syncthreads();
     double pm = 0.0;
     for (int j = tid; j < n; j += SM_THREADS) {
-        const double kv = rbf_pair(xs, X, cap, j, d, th);
+        double kv, gh = 0.0;
+        if constexpr (NU2 == 0) kv = rbf_pair(xs, X, cap, j, d, th);
+        else kv = matern_pair<NU2>(xs, il2, X, cap, j, d, th[0] * th[0], gh);
         ks[j] = kv;
+        if (UCB && NU2) hs[j] = gh;
         pm = fma(kv, al[j], pm);
     }
     const double mu = block_sum(pm, red, tid);        // also orders ks[] before the product below
@@ -105,12 +144,14 @@ __global__ __launch_bounds__(SM_THREADS) void small_posterior_kernel(int n, int 
     __syncthreads();
     // D(j, k) = d k(x*, X_j) / d x*_k = -k*_j (x*_k - X_jk) / l_k^2   (gradient(afterFirstArg = true), :95-107);
     // d mean / d x*_k = sum_j D(j,k) alpha_j;  d var / d x*_k = -2 sum_j D(j,k) w_j  (GPOptimizer.scala:97-101, derAfterVarFirst = 0)
+    // Matern: D(j, k) = -(sf^2 h_j) (x*_k - X_jk) / l_k^2, the same loop over hs
+    const double *gs = NU2 ? hs : ks;
     const double sd = sqrt(sig), coeff = kappa / (2.0 * sd);
     for (int k = wave; k < d; k += SM_THREADS / 64) {
         const double ls = th[1 + k], inv = 1.0 / (ls * ls), xk = xs[k];
         double dm = 0.0, dv = 0.0;
         for (int j = lane; j < n; j += 64) {
-            const double D = ((xk - X[j + (size_t)k * cap]) * inv) * (-ks[j]);
+            const double D = ((xk - X[j + (size_t)k * cap]) * inv) * (-gs[j]);
             dm = fma(D, al[j], dm);
             dv = fma(D, w[j], dv);
         }
@@ -148,18 +189,26 @@ __global__ __launch_bounds__(SM_THREADS) void small_trinv_kernel(int n, int cap,
 // info[g] = n + 1 (1-based failing pivot, as breeze's cholesky would fail on the extended matrix) when lambda^2 <= 0.
 // Nothing inside the leading n x n parts of L and L^-1 is written, and `alpha` is a buffer of its own (never the batch's current
 // one): whether the append counts is decided by the host over ALL models, and until then every model still reads as before.
+template <int NU2>
 __global__ __launch_bounds__(SM_THREADS) void small_append_kernel(int n, int cap, int d, double extra, const double *__restrict__ X,
                                                                   const double *__restrict__ Y, double *__restrict__ L, double *__restrict__ Linv,
                                                                   double *__restrict__ alpha, const double *__restrict__ theta, int *__restrict__ info) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *ks = sm, *l = sm + cap, *t = l + cap, *xs = t + cap, *red = xs + 64;
+    double *ks = sm, *l = sm + cap, *t = l + cap, *xs = t + cap, *il2 = xs + 64, *red = il2 + (NU2 ? 64 : 0);
     const int tid = threadIdx.x, g = blockIdx.x, lane = tid & 63, wave = tid >> 6;
     const double *th = theta + (size_t)g * (d + 2);
     double *Lg = L + (size_t)g * cap * cap, *Li = Linv + (size_t)g * cap * cap, *al = alpha + (size_t)g * cap;
     const double *y = Y + (size_t)g * cap;
-    if (tid < d) xs[tid] = X[n + (size_t)tid * cap];
+    if (tid < d) {
+        xs[tid] = X[n + (size_t)tid * cap];
+        if (NU2) il2[tid] = 1.0 / (th[1 + tid] * th[1 + tid]);
+    }
     __syncthreads();
-    for (int j = tid; j < n; j += SM_THREADS) ks[j] = rbf_pair(xs, X, cap, j, d, th);
+    for (int j = tid; j < n; j += SM_THREADS) {
+        [[maybe_unused]] double gh;
+        if constexpr (NU2 == 0) ks[j] = rbf_pair(xs, X, cap, j, d, th);
+        else ks[j] = matern_pair<NU2>(xs, il2, X, cap, j, d, th[0] * th[0], gh);
+    }
     __syncthreads();
     double ps = 0.0;
     for (int r = tid; r < n; r += SM_THREADS) {
@@ -200,7 +249,12 @@ __global__ __launch_bounds__(SM_THREADS) void small_append_kernel(int n, int cap
     }
 }
 
-size_t small_lds(int cap, int arrays) { return sizeof(double) * ((size_t)arrays * cap + 64 + SM_THREADS + 8); }
+// `arrays` vectors of cap doubles, xs, the reduction tree; a Matern kernel (kind 2 / 3) also holds il2.  The largest: Matern UCB at
+// cap = 2048 with ks, v, w and hs = 68 672 B.
+size_t small_lds(int cap, int arrays, int kind = 0) { return sizeof(double) * ((size_t)arrays * cap + 64 + (kind ? 64 : 0) + SM_THREADS + 8); }
+
+// LAUNCH(NU2) with the NU2 of a handle's kind
+#define SMALL_BY_KIND(kind, LAUNCH) do { if ((kind) == 0) { LAUNCH(0); } else if ((kind) == 2) { LAUNCH(3); } else { LAUNCH(5); } } while (0)
 
 gp_status small_alloc(gp_ctx *ctx, int n, int d, int G, int capacity, gp_small **out) {
     gp_small *s = new (std::nothrow) gp_small();
@@ -230,13 +284,23 @@ gp_status small_alloc(gp_ctx *ctx, int n, int d, int G, int capacity, gp_small *
     return GP_OK;
 }
 
-gp_status small_set_lds(gp_ctx *ctx, int cap) {
-    static int done_for = 0;
-    if (cap <= done_for) return GP_OK;
-    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 2)));
-    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 3)));
-    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_append_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 3)));
-    done_for = GP_SMALL_MAX_N;
+template <int NU2>
+gp_status small_set_lds_for(gp_ctx *ctx) {
+    const int kind = (NU2 + 1) / 2;
+    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<false, NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 2, kind)));
+    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<true, NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, NU2 ? 4 : 3, kind)));
+    GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_append_kernel<NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 3, kind)));
+    return GP_OK;
+}
+
+// once per process and kernel family (the RBF kernels' limits are not touched by a Matern handle, nor the other way round)
+gp_status small_set_lds(gp_ctx *ctx, int kind) {
+    static bool done[4] = {false, false, false, false};
+    if (done[kind]) return GP_OK;
+#define SM_SET(NU2) GP_TRY(small_set_lds_for<NU2>(ctx))
+    SMALL_BY_KIND(kind, SM_SET);
+#undef SM_SET
+    done[kind] = true;
     return GP_OK;
 }
 
@@ -346,19 +410,19 @@ gp_status gpi_ucb_lbfgs_lockstep(int d, const double *starts, int c, int lds, in
 }
 
 
-extern "C" {
-
-gp_status gp_small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl,
-                                const double *alphas, int capacity, gp_small **out) {
+// The two constructors, for every kernel: nu2 = 0 is ARD-RBF (gp_small_from_factors, gp_small_fit), 3 / 5 the Matern entry points.
+static gp_status small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl,
+                                    const double *alphas, int nu2, int capacity, gp_small **out) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
     GP_REQUIRE(ctx, X && thetas && Ls && alphas, "null pointer");
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && G >= 1 && ldx >= n && ldl >= n && std::max(n, capacity) <= GP_SMALL_MAX_N,
                "need 1 <= n <= capacity <= GP_SMALL_MAX_N, 1 <= d <= 64, G >= 1");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    GP_TRY(small_set_lds(ctx, std::max(n, capacity)));
+    GP_TRY(small_set_lds(ctx, (nu2 + 1) / 2));
     gp_small *s = nullptr;
     GP_TRY(small_alloc(ctx, n, d, G, capacity, &s));
+    s->kind = (nu2 + 1) / 2;
     const int cap = s->cap, P = d + 2;
     s->thetas.assign(thetas, thetas + (size_t)G * P);
     gp_status st = gpi_upload_2d(ctx, s->dX, cap, X, ldx, n, d);
@@ -375,8 +439,8 @@ gp_status gp_small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int 
     return GP_OK;
 }
 
-gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *Y, int ldy, int G, const double *thetas,
-                       double sigma_noise, int capacity, gp_small **out, int *info) {
+static gp_status small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *Y, int ldy, int G, const double *thetas, int nu2,
+                           double sigma_noise, int capacity, gp_small **out, int *info) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
     if (info) *info = 0;
@@ -384,9 +448,10 @@ gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && G >= 1 && ldx >= n && ldy >= n && std::max(n, capacity) <= GP_SMALL_MAX_N,
                "need 1 <= n <= capacity <= GP_SMALL_MAX_N, 1 <= d <= 64, G >= 1");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    GP_TRY(small_set_lds(ctx, std::max(n, capacity)));
+    GP_TRY(small_set_lds(ctx, (nu2 + 1) / 2));
     gp_small *s = nullptr;
     GP_TRY(small_alloc(ctx, n, d, G, capacity, &s));
+    s->kind = (nu2 + 1) / 2;
     const int cap = s->cap, P = d + 2;
     s->thetas.assign(thetas, thetas + (size_t)G * P);
     s->sigma_noise = sigma_noise;
@@ -399,7 +464,8 @@ gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
     for (int g = 0; g < G && st == GP_OK; ++g) {
         gp_model *m = nullptr;
         int h = 0;
-        st = gp_fit_rbf_dev(ctx, s->dX, n, d, cap, s->dY + (size_t)g * cap, thetas + (size_t)g * P, sigma_noise, &m, &h);
+        if (nu2 == 0) st = gp_fit_rbf_dev(ctx, s->dX, n, d, cap, s->dY + (size_t)g * cap, thetas + (size_t)g * P, sigma_noise, &m, &h);
+        else st = gp_fit_matern_dev(ctx, s->dX, n, d, cap, s->dY + (size_t)g * cap, thetas + (size_t)g * P, nu2, sigma_noise, &m, &h);
         if (st != GP_OK) { if (info) *info = h; break; }
         gpk_copy_2d(ctx->stream, s->dL + (size_t)g * cap * cap, cap, m->dL, m->ldl, n, n);
         gpk_zero_upper(ctx->stream, s->dL + (size_t)g * cap * cap, n, cap);
@@ -411,6 +477,34 @@ gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
     GP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out = s;
     return GP_OK;
+}
+
+extern "C" {
+
+gp_status gp_small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl,
+                                const double *alphas, int capacity, gp_small **out) {
+    return small_from_factors(ctx, X, n, d, ldx, thetas, G, Ls, ldl, alphas, 0, capacity, out);
+}
+
+gp_status gp_small_from_factors_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl,
+                                       const double *alphas, int nu2, int capacity, gp_small **out) {
+    if (!ctx || !out) return GP_EINVAL;
+    *out = nullptr;
+    GP_REQUIRE(ctx, nu2 == 3 || nu2 == 5, "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
+    return small_from_factors(ctx, X, n, d, ldx, thetas, G, Ls, ldl, alphas, nu2, capacity, out);
+}
+
+gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *Y, int ldy, int G, const double *thetas,
+                       double sigma_noise, int capacity, gp_small **out, int *info) {
+    return small_fit(ctx, X, n, d, ldx, Y, ldy, G, thetas, 0, sigma_noise, capacity, out, info);
+}
+
+gp_status gp_small_fit_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *Y, int ldy, int G, const double *thetas, int nu2,
+                              double sigma_noise, int capacity, gp_small **out, int *info) {
+    if (!ctx || !out) return GP_EINVAL;
+    *out = nullptr;
+    GP_REQUIRE(ctx, nu2 == 3 || nu2 == 5, "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
+    return small_fit(ctx, X, n, d, ldx, Y, ldy, G, thetas, nu2, sigma_noise, capacity, out, info);
 }
 
 void gp_small_destroy(gp_small *s) {
@@ -453,8 +547,10 @@ gp_status gp_small_posterior(gp_small *s, const double *Xs, int m, int ldxs, dou
     GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * s->d, &dXs));
     GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)2 * m * s->G, &dout));
     GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, s->d));
-    hipLaunchKernelGGL(small_posterior_kernel<false>, dim3(m, s->G), dim3(SM_THREADS), small_lds(s->cap, 2), ctx->stream, s->n, s->cap, s->d, 0,
-                       s->dX, s->dLinv, s->dalpha, s->dtheta, dXs, m, m, 0.0, dout, dout + (size_t)m * s->G, nullptr);
+#define SM_POST(NU2) hipLaunchKernelGGL((small_posterior_kernel<false, NU2>), dim3(m, s->G), dim3(SM_THREADS), small_lds(s->cap, 2, s->kind), ctx->stream, s->n, \
+                                        s->cap, s->d, 0, s->dX, s->dLinv, s->dalpha, s->dtheta, dXs, m, m, 0.0, dout, dout + (size_t)m * s->G, nullptr)
+    SMALL_BY_KIND(s->kind, SM_POST);
+#undef SM_POST
     GP_LAUNCH_CHECK(ctx);
     GP_TRY(gpi_download_2d(ctx, mean, m * s->G, dout, m * s->G, m * s->G, 1));
     return gpi_download_2d(ctx, var, m * s->G, dout + (size_t)m * s->G, m * s->G, m * s->G, 1);
@@ -470,8 +566,10 @@ gp_status gp_small_ucb(gp_small *s, int g, const double *Xs, int m, int ldxs, do
     GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * s->d, &dXs));
     GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)m * (1 + s->d), &dout));
     GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, s->d));
-    hipLaunchKernelGGL(small_posterior_kernel<true>, dim3(m), dim3(SM_THREADS), small_lds(s->cap, 3), ctx->stream, s->n, s->cap, s->d, g, s->dX,
-                       s->dLinv, s->dalpha, s->dtheta, dXs, m, m, kappa, dout, nullptr, dout + m);
+#define SM_UCB(NU2) hipLaunchKernelGGL((small_posterior_kernel<true, NU2>), dim3(m), dim3(SM_THREADS), small_lds(s->cap, NU2 ? 4 : 3, s->kind), ctx->stream, s->n, \
+                                       s->cap, s->d, g, s->dX, s->dLinv, s->dalpha, s->dtheta, dXs, m, m, kappa, dout, nullptr, dout + m)
+    SMALL_BY_KIND(s->kind, SM_UCB);
+#undef SM_UCB
     GP_LAUNCH_CHECK(ctx);
     GP_TRY(gpi_download_2d(ctx, value, m, dout, m, m, 1));
     return gpi_download_2d(ctx, grad, m * s->d, dout + m, m * s->d, m * s->d, 1);
@@ -494,8 +592,10 @@ gp_status gp_small_append(gp_small *s, const double *x_new, const double *y_new,
     GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(int) * (size_t)s->G + 16, &dscr));
     dinfo = reinterpret_cast<int *>(dscr);
     GP_HIP(ctx, hipMemsetAsync(dinfo, 0, sizeof(int) * s->G, ctx->stream));
-    hipLaunchKernelGGL(small_append_kernel, dim3(s->G), dim3(SM_THREADS), small_lds(cap, 3), ctx->stream, n, cap, s->d,
-                       std::isnan(s->sigma_noise) ? 0.0 : s->sigma_noise, s->dX, s->dY, s->dL, s->dLinv, s->dalpha_next, s->dtheta, dinfo);
+#define SM_APPEND(NU2) hipLaunchKernelGGL(small_append_kernel<NU2>, dim3(s->G), dim3(SM_THREADS), small_lds(cap, 3, s->kind), ctx->stream, n, cap, s->d, \
+                                          std::isnan(s->sigma_noise) ? 0.0 : s->sigma_noise, s->dX, s->dY, s->dL, s->dLinv, s->dalpha_next, s->dtheta, dinfo)
+    SMALL_BY_KIND(s->kind, SM_APPEND);
+#undef SM_APPEND
     GP_LAUNCH_CHECK(ctx);
     GP_HIP(ctx, hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * s->G, hipMemcpyDeviceToHost, ctx->stream));
     GP_HIP(ctx, hipStreamSynchronize(ctx->stream));

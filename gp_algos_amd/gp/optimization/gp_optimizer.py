@@ -11,7 +11,9 @@ The random draws (initial grid, L-BFGS starting points) come from numpy instead 
 commons-math: the reference's trajectory is not reproducible by construction.
 Past GP_SMALL_MAX_N observations the loop continues on the large regression model (RegressionModel.maximize_ucb over
 gp_predict_grad): it is fitted once, when the small batch is full, and every accepted point after that is appended to it in O(n^2)
-(RegressionModel.append, gp_model_append) -- factor, t, LML and the cached matrices of the posterior are extended, nothing is refitted."""
+(RegressionModel.append, gp_model_append) -- factor, t, LML and the cached matrices of the posterior are extended, nothing is refitted.
+A MaternKernel (nu = 3/2, 5/2) runs the same loop on a Matern small batch (gp_small_fit_matern); the large model has no Matern UCB, so
+such a run is limited to GP_SMALL_MAX_N observations and `maximize` says so before it evaluates anything."""
 from dataclasses import dataclass
 from typing import Sequence
 
@@ -20,7 +22,7 @@ import numpy as np
 from ... import default_context
 from ..._lib import GP_SMALL_MAX_N
 from ...core import RegressionModel, SmallModelBatch
-from ...utils.kernel_requisites import GaussianRbfKernel
+from ...utils.kernel_requisites import GaussianRbfKernel, MaternKernel
 from ...utils.stats_utils import meanAndVarOfData
 
 
@@ -49,8 +51,15 @@ class GPOptimizer:
         ranges, m, c, k = params.ranges, params.mParam, params.cParam, params.kParam
         if not (c >= 1 and m >= 1):
             raise ValueError("requirement failed: Params m and c needs to be greater or equal 1")
-        if not isinstance(self.gpPredictor.kernelFunc, GaussianRbfKernel):
-            raise NotImplementedError("the device UCB gradient is implemented for GaussianRbfKernel")
+        kf = self.gpPredictor.kernelFunc
+        if not isinstance(kf, (GaussianRbfKernel, MaternKernel)):
+            raise NotImplementedError("the device UCB gradient is implemented for GaussianRbfKernel and MaternKernel")
+        matern = isinstance(kf, MaternKernel)
+        kernel = ("matern32" if kf.nu2 == 3 else "matern52") if matern else "rbf"
+        if matern and 3 * len(ranges) + m > GP_SMALL_MAX_N:
+            # the Matern UCB gradient and append exist on the small batch only (the large model refuses a Matern model)
+            raise ValueError("GP-UCB with a MaternKernel holds at most GP_SMALL_MAX_N = %d observations: %d initial points + %d iterations"
+                             % (GP_SMALL_MAX_N, 3 * len(ranges), m))
         pointGrid = self.prepareGrid(ranges)
         evaluated = self.evaluateGridPoints(pointGrid, func)
         hp = self.hyperParams
@@ -61,7 +70,7 @@ class GPOptimizer:
         # up to GP_SMALL_MAX_N observations the batched small-n path with its O(n^2) append; past it the large model (gp_fit_rbf,
         # gp_model_maximize_ucb), fitted once and appended to per accepted point (gp_model_append)
         cap = min(n0 + m, GP_SMALL_MAX_N)
-        batch = SmallModelBatch(ctx, pointGrid, theta[None, :], Y=evaluated[:, None], sigma_noise=self.noise, capacity=cap) if n0 <= cap else None
+        batch = SmallModelBatch(ctx, pointGrid, theta[None, :], Y=evaluated[:, None], sigma_noise=self.noise, capacity=cap, kernel=kernel) if n0 <= cap else None
         large = None if batch is not None else RegressionModel(ctx, pointGrid, evaluated, theta, sigma_noise=self.noise)
         points, values = [row.copy() for row in pointGrid], list(evaluated)
         try:

@@ -146,6 +146,74 @@ class GaussianRbfKernel(KernelFunc):
         return self.gradient(afterFirstArg)(points[0], points[1])
 
 
+class MaternKernel(KernelFunc):
+    """ARD Matern kernel, nu = nu2 / 2 with nu2 in {3, 5} (no counterpart in the reference; the formulas of include/gpcore.h), hyper-parameters
+    laid out as GaussianRbfParams(signalVar, lengthScales, noiseVar).  With z_k = (x_k - y_k) / l_k, r^2 = sum z_k^2, a = sqrt(nu2 r^2):
+        nu = 3/2:  k = sf^2 (1 + a) exp(-a),            h = 3 exp(-a)
+        nu = 5/2:  k = sf^2 (1 + a + a^2 / 3) exp(-a),  h = 5/3 (1 + a) exp(-a)
+    plus noiseVar^2 on equal indices; dk/dx_k = -sf^2 h (x_k - y_k) / l_k^2 (0 at r = 0), dk/dl_k = sf^2 h z_k^2 / l_k."""
+
+    def __init__(self, nu2, params):
+        if nu2 not in (3, 5):
+            raise ValueError("nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)")
+        self.nu2 = int(nu2)
+        self.params = params
+
+    def _terms(self, a, b):   # (k / sf^2, h), the device's operation order
+        r2 = 0.0
+        for k in range(self.params.lengthScales.size):
+            diff = float(a[k]) - float(b[k])
+            ls = float(self.params.lengthScales[k])
+            r2 = r2 + (diff * (1.0 / (ls * ls))) * diff
+        s = math.sqrt(self.nu2 * r2)
+        e = math.exp(-s)
+        if self.nu2 == 3:
+            return (1.0 + s) * e, 3.0 * e
+        return (1.0 + s * (1.0 + s * (1.0 / 3.0))) * e, (5.0 / 3.0) * ((1.0 + s) * e)
+
+    def apply(self, obj1, obj2, sameIndex):
+        sf, sn = self.params.signalVar, self.params.noiseVar
+        v = sf * sf * self._terms(obj1, obj2)[0]
+        return v + sn * sn if sameIndex else v
+
+    @property
+    def hyperParametersNum(self):
+        return self.params.lengthScales.size + 2
+
+    def derAfterHyperParam(self, paramNum):   # paramNum is 1-based, as GaussianRbfKernel's
+        d = self.params.lengthScales.size
+        sf, sn = self.params.signalVar, self.params.noiseVar
+
+        def f(vec1, vec2, sameIndex):
+            if paramNum == 1:
+                return 2 * sf * self._terms(vec1, vec2)[0]
+            if paramNum < d + 2:
+                diff = float(vec1[paramNum - 2]) - float(vec2[paramNum - 2])
+                return sf * sf * self._terms(vec1, vec2)[1] * diff * diff * math.pow(float(self.params.lengthScales[paramNum - 2]), -3)
+            if paramNum == d + 2:
+                return 2 * sn if sameIndex else 0.0
+            raise MatchError(paramNum)
+        return f
+
+    def changeHyperParams(self, dv):
+        return MaternKernel(self.nu2, self.params.fromDenseVector(dv))
+
+    @property
+    def hyperParams(self):
+        return self.params
+
+    def gradient(self, afterFirstArg):
+        def g(vec1, vec2):
+            diff = np.asarray(vec1, dtype=np.float64) - np.asarray(vec2, dtype=np.float64)
+            inv = 1.0 / (self.params.lengthScales * self.params.lengthScales)
+            gh = self.params.signalVar * self.params.signalVar * self._terms(vec1, vec2)[1]
+            return (diff * inv) * (-gh) if afterFirstArg else (diff * inv) * gh
+        return g
+
+    def gradientAt(self, afterFirstArg, points):
+        return self.gradient(afterFirstArg)(points[0], points[1])
+
+
 def testTrainKernelMatrix(test, train, kernelFun):   # :116-124
     from .matrix_utils import buildKernelMatrix
     return buildKernelMatrix(kernelFun, test, train)

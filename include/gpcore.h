@@ -331,6 +331,19 @@ gp_status gp_small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
 /* The same from factors the caller holds: Ls = G matrices (n x n, leading dimension ldl, model g at Ls + g*ldl*n), alphas G x n.
  * Such a batch cannot be appended to (it carries no targets). */
 gp_status gp_small_from_factors(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl, const double *alphas, int capacity, gp_small **out);
+/* The same two constructors for the ARD Matern kernels (nu2 = 2 nu: 3 or 5, anything else GP_EINVAL; theta as above): the models are
+ * fitted through gp_fit_matern_dev.  Every gp_small_* call below works on such a handle as on an ARD-RBF one; handles from the two
+ * constructors above are ARD-RBF and unchanged.  With z_k = (x*_k - X_jk) / l_k, r^2 = sum_k z_k^2, a = sqrt(nu2) r:
+ *     nu = 3/2:  k = sf^2 (1 + a) exp(-a),              h = 3 exp(-a)
+ *     nu = 5/2:  k = sf^2 (1 + a + a^2 / 3) exp(-a),    h = 5/3 (1 + a) exp(-a)
+ * each pair from its differences ((diff l^-2) diff summed, then sqrt / polynomial / exp), and the input derivative gp_small_ucb uses is
+ *     d k(x*, X_j) / d x*_k = -sf^2 h_j (x*_k - X_jk) / l_k^2
+ * which divides by nothing and is 0 at r = 0 (for nu = 3/2, where the kernel has a kink there, the subgradient that the length-scale
+ * derivative of gp_lml_grad_matern_batched takes too).  With it d mean / d x*_k = sum_j D_jk alpha_j and d var / d x*_k = -2 sum_j D_jk w_j,
+ * w = L^-T L^-1 k*.  The large model's gp_predict_grad*, gp_model_ucb, gp_model_maximize_ucb and gp_model_append* still refuse a Matern
+ * model: GP-UCB with a Matern kernel runs on these batches, up to GP_SMALL_MAX_N observations. */
+gp_status gp_small_fit_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *Y, int ldy, int G, const double *thetas, int nu2, double sigma_noise, int capacity, gp_small **out, int *info);
+gp_status gp_small_from_factors_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *thetas, int G, const double *Ls, int ldl, const double *alphas, int nu2, int capacity, gp_small **out);
 void gp_small_destroy(gp_small *small);
 gp_status gp_small_size(const gp_small *small, int *n, int *capacity, int *G);
 enum { GP_SMALL_GET_L = 0, GP_SMALL_GET_LINV = 1, GP_SMALL_GET_ALPHA = 2 };
