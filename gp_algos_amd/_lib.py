@@ -96,6 +96,9 @@ SIGNATURES = {
     "gp_fit_matern_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _i, _d, C.POINTER(_vp), _ip]),
     "gp_lml_grad_matern_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
+    "gp_model_loo": (_i, [_vp, _dp, _dp, _dp]),
+    "gp_loo_grad_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
+    "gp_optimize_loo": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
     "gp_small_fit":(_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
     "gp_small_from_factors": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_vp)]),
     "gp_small_fit_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _i, _d, _i, C.POINTER(_vp), _ip]),

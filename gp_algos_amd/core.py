@@ -259,6 +259,45 @@ class Context:
                                                 int(history), L.dptr(out), L.dptr(lml), C.byref(its), C.byref(evs)))
         return out, float(lml[0]), its.value, evs.value
 
+    # -- leave-one-out cross-validation (Rasmussen & Williams eqs. 5.10-5.13); kernel = "rbf", "matern32" or "matern52" ---------------------
+    @staticmethod
+    def _loo_kernel(kernel):
+        if kernel not in ("rbf", "matern32", "matern52"):
+            raise ValueError("kernel must be 'rbf', 'matern32' or 'matern52'")
+        return {"rbf": 0, "matern32": 3, "matern52": 5}[kernel]
+
+    def loo_grad_batched(self, X, y, thetas, kernel="rbf", nparams=None, sigma_noise=None):
+        """gp_loo_grad_batched: (logp[B], grad[B, nparams], info[B]) of the leave-one-out log predictive probability."""
+        code = self._loo_kernel(kernel)
+        X, y = L.f64(X), L.f64(y)
+        n, d = X.shape
+        thetas = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+        B, P = thetas.shape
+        if P != d + 2 or y.size != n:
+            raise ValueError("dimension mismatch")
+        nparams = P if nparams is None else int(nparams)
+        logp, grad, info = np.zeros(B), np.zeros((B, max(nparams, 1))), np.zeros(B, dtype=np.int32)
+        sn = float("nan") if sigma_noise is None else float(sigma_noise)
+        self.check(self._lib.gp_loo_grad_batched(self.h, L.dptr(X), n, d, n, L.dptr(y), L.dptr(thetas), B, nparams, code, sn,
+                                                 L.dptr(logp), L.dptr(grad), info.ctypes.data_as(C.POINTER(C.c_int))))
+        return logp, grad[:, :nparams], info
+
+    def optimize_loo(self, X, y, theta0, kernel="rbf", nparams=None, sigma_noise=None, max_iter=20, history=4):
+        """gp_optimize_loo: (theta*, L_LOO(theta*), iterations, evaluations)."""
+        code = self._loo_kernel(kernel)
+        X, y = L.f64(X), L.f64(y)
+        n, d = X.shape
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+        if theta0.size != d + 2 or y.size != n:
+            raise ValueError("dimension mismatch")
+        nparams = d + 2 if nparams is None else int(nparams)
+        out, logp = np.zeros(d + 2), np.zeros(1)
+        its, evs = C.c_int(0), C.c_int(0)
+        sn = float("nan") if sigma_noise is None else float(sigma_noise)
+        self.check(self._lib.gp_optimize_loo(self.h, L.dptr(X), n, d, n, L.dptr(y), L.dptr(theta0), nparams, code, sn, int(max_iter),
+                                             int(history), L.dptr(out), L.dptr(logp), C.byref(its), C.byref(evs)))
+        return out, float(logp[0]), its.value, evs.value
+
     def posterior_from_factor(self, X, theta, Lm, alpha, Xs, full_cov=False, want_v=False):
         """gp_posterior_from_factor (GpPredictor.computePosterior with the ARD-RBF kernel): (mean, var, cov|None, V|None)."""
         X, theta, Lm, alpha, Xs = L.f64(X), L.f64(theta), L.f64(Lm), L.f64(alpha), L.f64(Xs)
@@ -437,6 +476,13 @@ class RegressionModel:
         out = np.zeros(1)
         self.ctx.check(self.ctx._lib.gp_model_get(self.h, L.GP_GET_LML, L.dptr(out), 1))
         return float(out[0])
+
+    def loo(self):
+        """gp_model_loo: (mean[n], var[n], logp) -- the leave-one-out predictive mean and variance of every training point and the
+        leave-one-out log predictive probability (Rasmussen & Williams eqs. 5.10-5.12)."""
+        mean, var, logp = np.zeros(self.n), np.zeros(self.n), np.zeros(1)
+        self.ctx.check(self.ctx._lib.gp_model_loo(self.h, L.dptr(mean), L.dptr(var), L.dptr(logp)))
+        return mean, var, float(logp[0])
 
     def append(self, X_new, y_new):
         """gp_model_append: extend the fitted model by one point (d values) or k points (k x d) in O(k n^2) -- afterwards it is the

@@ -141,6 +141,20 @@ void gpk_matern_gram_cross(hipStream_t s, const double *Xs, int m, int ldxs, con
 void gpk_matern_lml_grad_traces(hipStream_t s, const double *X, int n, int d, int ldx, const double *theta, int nu2, const double *alpha, const double *Kinv,
                                 int ldk, double *partials, double *out);
 int gpk_matern_trace_partials_size(int d);
+// Leave-one-out cross-validation (kernels_loo.hip; Rasmussen & Williams eqs. 5.10-5.13).  np: the padded size, a multiple of GP_NB.
+constexpr int GP_LOO_CHUNKS = 16;     // column chunks of gpk_loo_diag and of the row part of gpk_loo_symv_lower
+// partial[GP_LOO_CHUNKS x np]: chunk sums of kappa_i = sum_{j >= i} T(i, j)^2 for the upper-triangular T = L^-T (np x np, ld = np)
+void gpk_loo_diag(hipStream_t s, const double *T, int np, double *partial);
+// kappa_i = sum_{q < nch} kap[q * sc + i * si]  ->  mean, var, u = alpha / kappa, c = (1 + alpha^2 / kappa) / kappa (np each, zeros from n on) and
+// logp[0] = sum_i [ 1/2 log kappa_i - alpha_i^2 / (2 kappa_i) ] - n/2 log 2 pi;  bpart: (np + 255) / 256 doubles of scratch
+void gpk_loo_terms(hipStream_t s, const double *kap, int nch, size_t sc, size_t si, const double *alpha, const double *y, int n, int np, double *mean,
+                   double *var, double *u, double *c, double *bpart, double *logp);
+// out[0..n) = A x, A symmetric n x n with only its lower triangle valid; partial: (GP_LOO_CHUNKS + 1) x n doubles of scratch
+void gpk_loo_symv_lower(hipStream_t s, const double *A, int ld, int n, const double *x, double *partial, double *out);
+// Kinv (np x np, ld = np, lower valid) is mirrored into its upper triangle in place; S (np x np, ld = np) = Kinv diag(c)
+void gpk_loo_mirror_scale(hipStream_t s, double *Kinv, int np, const double *c, double *S);
+// Q(i, j) -= alpha_i b_j + b_i alpha_j on the lower triangle, i < n
+void gpk_loo_weight(hipStream_t s, double *Q, int ld, int n, const double *alpha, const double *b);
 // Co2Kernel (gp/regression/Co2Prediction.scala:29-137), 1-D inputs, theta = hp1..hp11 on the host; pos = 0: kernel, 1..11: derivative
 void gpk_co2_gram(hipStream_t s, const double *xr, int nr, const double *xc, int nc, const double *theta, int pos, double *K, int ldk, int sym,
                   int full, double extra);

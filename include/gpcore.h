@@ -316,6 +316,27 @@ gp_status gp_lml_grad_matern_batched(gp_ctx *ctx, const double *X, int n, int d,
 /* L-BFGS on the first nparams hyper-parameters (m = history, maxIter = max_iter, best-seen point), as gp_optimize_rbf. */
 gp_status gp_optimize_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int nu2, double sigma_noise, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out, int *evals_out);
 
+/* ---- leave-one-out cross-validation ------------------------------------------------------------ */
+/* Rasmussen & Williams, Gaussian Processes for Machine Learning, section 5.4.2, eqs. 5.10-5.13.  With kappa_i = [K^-1]_ii:
+ *     mu_i = y_i - alpha_i / kappa_i,   sigma_i^2 = 1 / kappa_i                                                   (5.12)
+ *     L_LOO = sum_i [ 1/2 log kappa_i - alpha_i^2 / (2 kappa_i) ] - n/2 log 2 pi                                  (5.10, 5.11)
+ *     dL_LOO / dtheta_p = 1/2 tr( (alpha b^T + b alpha^T - Q2) dK/dtheta_p )                                      (5.13, as one trace)
+ *     u_i = alpha_i / kappa_i,   b = K^-1 u,   c_i = (1 + alpha_i^2 / kappa_i) / kappa_i,   Q2 = K^-1 diag(c) K^-1.
+ * gp_model_loo (eqs. 5.10-5.12): the leave-one-out predictive mean[n] and var[n] of every training point and *logp = L_LOO (one double),
+ * host outputs, any of them NULL = not wanted.  Any fitted model that holds its targets and a factor: gp_fit_rbf*, gp_fit_matern*,
+ * gp_fit_co2, gp_fit_from_gram (which keeps y), appended models; a model that keeps no y is refused with GP_EINVAL.  GP_ENOTPD if the
+ * model's last (re)fit failed, learnt as gp_predict_grad_dev learns it.  Costs the triangular inversion (n^3 / 3 flops): kappa is taken
+ * from L^-T, K^-1 is never formed.  The model itself is not changed. */
+gp_status gp_model_loo(gp_model *model, double *mean, double *var, double *logp);
+/* L_LOO (eqs. 5.10, 5.11) and its gradient (eq. 5.13) at B settings (thetas B x (d + 2) row-major, theta = (sf, l_1..l_d, sn)), one setting at
+ * a time through a resident model.  kernel: 0 = ARD-RBF, 3 = ARD Matern 3/2, 5 = ARD Matern 5/2, anything else GP_EINVAL.  nparams,
+ * sigma_noise (NaN = none; added to the diagonal as gp_model_refit_dev adds it) and info as for gp_lml_grad_matern_batched: grad is
+ * B x nparams, the first nparams <= d + 2 components; a setting whose matrix is not positive definite gets NaN and its pivot in info[b],
+ * and the batch goes on.  1 <= d <= 64. */
+gp_status gp_loo_grad_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *thetas, int B, int nparams, int kernel, double sigma_noise, double *logp, double *grad, int *info);
+/* L-BFGS on the first nparams hyper-parameters maximising L_LOO (eqs. 5.10-5.13 through gp_loo_grad_batched), as gp_optimize_matern. */
+gp_status gp_optimize_loo(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int kernel, double sigma_noise, int max_iter, int history, double *theta_out, double *logp_out, int *iters_out, int *evals_out);
+
 /* ---- batched small-n posteriors: GP-UCB and GP-UKF --------------------------------------------- */
 /* The heaviest callers of GpPredictor.computePosterior (gp/regression/GpPredictor.scala:45-58) ask for ONE test point per call
  * against a few hundred training points: GPOptimizer.maximizeUCB (gp/optimization/GPOptimizer.scala:82-109) inside L-BFGS, and
