@@ -96,6 +96,10 @@ SIGNATURES = {
     "gp_fit_matern_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _i, _d, C.POINTER(_vp), _ip]),
     "gp_lml_grad_matern_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
+    "gp_kernel_matmul": (_i, [_vp, _i, _dp, _i, _i, _dp, _i, _i, _i, _dp, _dp, _i, _i, _dp, _i]),
+    "gp_kernel_matmul_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _dp, _vp, _i, _i, _vp, _i]),
+    "gp_predict_mean": (_i, [_vp, _dp, _i, _i, _dp]),
+    "gp_predict_mean_dev": (_i, [_vp, _vp, _i, _i, _vp]),
     "gp_model_loo": (_i, [_vp, _dp, _dp, _dp]),
     "gp_loo_grad_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_loo": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),

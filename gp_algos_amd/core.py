@@ -298,6 +298,21 @@ class Context:
                                              int(history), L.dptr(out), L.dptr(logp), C.byref(its), C.byref(evs)))
         return out, float(logp[0]), its.value, evs.value
 
+    def kernel_matmul(self, Xs, X, theta, A, kernel="rbf"):
+        """gp_kernel_matmul: K(Xs, X; theta) @ A with the m x n kernel matrix never stored; A is n x T (-> m x T) or 1-D (-> 1-D)."""
+        code = self._loo_kernel(kernel)
+        Xs, X, theta = L.f64(Xs), L.f64(X), L.f64(theta)
+        vec = np.ndim(A) == 1
+        A = np.asarray(A, dtype=np.float64)
+        A = L.f64(A.reshape(-1, 1) if vec else A)
+        (m, d), (n, T) = Xs.shape, A.shape
+        if X.shape != (n, d) or theta.size != d + 2:
+            raise ValueError("dimension mismatch")
+        Cm = np.zeros((m, T), order="F")
+        self.check(self._lib.gp_kernel_matmul(self.h, code, L.dptr(Xs), m, max(m, 1), L.dptr(X), n, max(n, 1), d, L.dptr(theta), L.dptr(A), T, max(n, 1),
+                                              L.dptr(Cm), max(m, 1)))
+        return Cm[:, 0].copy() if vec else Cm
+
     def posterior_from_factor(self, X, theta, Lm, alpha, Xs, full_cov=False, want_v=False):
         """gp_posterior_from_factor (GpPredictor.computePosterior with the ARD-RBF kernel): (mean, var, cov|None, V|None)."""
         X, theta, Lm, alpha, Xs = L.f64(X), L.f64(theta), L.f64(Lm), L.f64(alpha), L.f64(Xs)
@@ -514,6 +529,14 @@ class RegressionModel:
         self.ctx.check(self.ctx._lib.gp_predict(self.h, L.dptr(Xs), m, max(m, 1), L.dptr(mean), L.dptr(var),
                                                 L.dptr(cov) if full_cov else None, max(m, 1)))
         return mean, var, cov
+
+    def predict_mean(self, Xs):
+        """gp_predict_mean: the posterior mean alone, K(Xs, X) alpha without the m x n workspace and the row solve of predict()."""
+        Xs = self._test_points(Xs)
+        m = Xs.shape[0]
+        mean = np.zeros(m)
+        self.ctx.check(self.ctx._lib.gp_predict_mean(self.h, L.dptr(Xs), m, max(m, 1), L.dptr(mean)))
+        return mean
 
     def _test_points(self, Xs):
         Xs = np.asarray(Xs, dtype=np.float64)

@@ -155,6 +155,11 @@ gp_status gpi_model_alpha(gp_model *m, double *dst) {
     return GP_OK;
 }
 
+const double *gpi_model_alpha_dev(gp_model *m) {
+    ensure_alpha(m);
+    return m->dalpha;
+}
+
 // A stream whose work stays off `reserved` of the device's CUs (0, or a device of fewer than 64 CUs: no mask); a plain stream where
 // the masked one cannot be made.
 static hipError_t masked_stream_create(hipStream_t *sp, int num_cu, int reserved) {

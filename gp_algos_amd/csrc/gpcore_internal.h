@@ -141,6 +141,32 @@ void gpk_matern_gram_cross(hipStream_t s, const double *Xs, int m, int ldxs, con
 void gpk_matern_lml_grad_traces(hipStream_t s, const double *X, int n, int d, int ldx, const double *theta, int nu2, const double *alpha, const double *Kinv,
                                 int ldk, double *partials, double *out);
 int gpk_matern_trace_partials_size(int d);
+// k / sf^2 and h (d k / d l_k = sf^2 h z_k^2 / l_k) of the ARD Matern kernels from r^2 = sum_k z_k^2; h is dead code where it is not used
+template <int NU2>
+__device__ __forceinline__ void matern_terms(double r2, double &k0, double &h) {
+    const double a = sqrt((double)NU2 * r2), e = exp(-a);
+    if (NU2 == 3) {
+        k0 = (1.0 + a) * e;
+        h = 3.0 * e;
+    } else {
+        k0 = fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0) * e;
+        h = (5.0 / 3.0) * ((1.0 + a) * e);
+    }
+}
+// The far-point scan of the matrix-core Gram forms on its own (gram_far_kernel / matern_far_kernel): one thread per point of Xa (na x d) and
+// Xb (nb x d), |(x - c) / l|^2 against the kernel's norm limit (nu2 = 0: 64, 3: 21, 5: 38; NaN counts as far); a far point writes `epoch`
+// (gpk_gram_epoch) into *far_flag.  cen: d doubles with stride ldcen.
+void gpk_gram_far_scan(hipStream_t s, const double *Xa, int na, int ldxa, const double *Xb, int nb, int ldxb, int d, const double *theta,
+                       const double *cen, int ldcen, int *far_flag, int epoch);
+void gpk_matern_far_scan(hipStream_t s, int nu2, const double *Xa, int na, int ldxa, const double *Xb, int nb, int ldxb, int d, const double *theta,
+                         const double *cen, int ldcen, int *far_flag, int epoch);
+// Kernel-matrix product without the matrix (kernels_kmm.hip): C (m x T, ldc) = K(Xs, X; theta) A, K the ARD-RBF (nu2 = 0) or ARD Matern
+// (nu2 = 3, 5) cross-Gram of Xs (m x d) and X (n x d), never stored and never with a noise term; A is n x T (lda).  center: d doubles on
+// the device (the centre of the matrix-core r^2); far_flag as for gpk_gram_cross (nullptr: the per-pair form alone);
+// partials: gpk_kernel_matmul_partials(m, n, d, T) doubles of scratch.  m, n, T >= 1.
+size_t gpk_kernel_matmul_partials(int m, int n, int d, int T);
+void gpk_kernel_matmul(hipStream_t s, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta,
+                       const double *center, const double *A, int T, int lda, double *partials, double *C, int ldc, int *far_flag);
 // Leave-one-out cross-validation (kernels_loo.hip; Rasmussen & Williams eqs. 5.10-5.13).  np: the padded size, a multiple of GP_NB.
 constexpr int GP_LOO_CHUNKS = 16;     // column chunks of gpk_loo_diag and of the row part of gpk_loo_symv_lower
 // partial[GP_LOO_CHUNKS x np]: chunk sums of kappa_i = sum_{j >= i} T(i, j)^2 for the upper-triangular T = L^-T (np x np, ld = np)
@@ -231,6 +257,7 @@ gp_status gpi_download_2d(gp_ctx *ctx, double *dst, int ldd, const double *src, 
 gp_status gpi_read_info(gp_ctx *ctx, int *info);
 gp_ctx *gpi_child_ctx(gp_ctx *ctx, int k);
 gp_status gpi_model_alpha(gp_model *m, double *dst);
+const double *gpi_model_alpha_dev(gp_model *m);     // the model's own alpha (n doubles on the device), computed on demand in stream order
 gp_status gpi_model_alloc(gp_ctx *ctx, int n, int d, bool has_x, gp_model **out);
 // L-BFGS (`history` pairs, at most max_iter iterations, NC batched backtracking steps per iteration, best-seen rule) maximising
 // F over the first nparams entries of theta: the driver behind gp_optimize_rbf and gp_ep_optimize_rbf

@@ -524,6 +524,12 @@ static int next_epoch() {
 }
 int gpk_gram_epoch() { return next_epoch(); }     // the Matern builders (kernels_matern.hip) share the scan's flag, so they share its epochs
 
+void gpk_gram_far_scan(hipStream_t s, const double *Xa, int na, int ldxa, const double *Xb, int nb, int ldxb, int d, const double *theta,
+                       const double *cen, int ldcen, int *far_flag, int epoch) {
+    hipLaunchKernelGGL(gram_far_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, s, Xa, na, ldxa, Xb, nb, ldxb, d, make_params(theta, d, 0.0), cen, ldcen,
+                       far_flag, epoch);
+}
+
 template <int MODE>
 static void launch_unit(hipStream_t s, const double *Xr, int nr, int ldxr, const double *Xc, int nc, int ldxc, int d, const GramParams &p,
                         const double *cen, int ldcen, double *K, int ldk, int *far_flag, int epoch) {

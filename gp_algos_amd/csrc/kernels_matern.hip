@@ -54,18 +54,7 @@ __device__ __forceinline__ void matern_tile_lower(int t, int &bi, int &bj) {
     bj = t - b * (b + 1) / 2;
 }
 
-// k / sf^2 and h from r^2 (h is dead code in the Gram kernels)
-template <int NU2>
-__device__ __forceinline__ void matern_terms(double r2, double &k0, double &h) {
-    const double a = sqrt((double)NU2 * r2), e = exp(-a);
-    if (NU2 == 3) {
-        k0 = (1.0 + a) * e;
-        h = 3.0 * e;
-    } else {
-        k0 = fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0) * e;
-        h = (5.0 / 3.0) * ((1.0 + a) * e);
-    }
-}
+// (matern_terms: k / sf^2 and h from r^2, gpcore_internal.h -- kernels_kmm.hip evaluates the same kernels)
 
 // The scan: one thread per point, |z|^2 against the limit (NaN counts as far).  A far point writes this call's epoch into the flag.
 __global__ __launch_bounds__(256) void matern_far_kernel(const double *__restrict__ Xa, int na, int ldxa, const double *__restrict__ Xb, int nb, int ldxb,
@@ -479,6 +468,12 @@ void gpk_matern_gram_cross(hipStream_t s, const double *Xs, int m, int ldxs, con
     const int ldcen = center ? 1 : ldx;
     if (nu2 == 3) matern_gram_launch<3, false>(s, Xs, m, ldxs, X, n, ldx, d, p, cen, ldcen, Ks, ldks, 1, far_flag);
     else matern_gram_launch<5, false>(s, Xs, m, ldxs, X, n, ldx, d, p, cen, ldcen, Ks, ldks, 1, far_flag);
+}
+
+void gpk_matern_far_scan(hipStream_t s, int nu2, const double *Xa, int na, int ldxa, const double *Xb, int nb, int ldxb, int d, const double *theta,
+                         const double *cen, int ldcen, int *far_flag, int epoch) {
+    hipLaunchKernelGGL(matern_far_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, s, Xa, na, ldxa, Xb, nb, ldxb, d, matern_params(theta, d, 0.0), cen, ldcen,
+                       nu2 == 3 ? MATERN_NORM_LIMIT_3 : MATERN_NORM_LIMIT_5, far_flag, epoch);
 }
 
 int gpk_matern_trace_partials_size(int d) { return MTR_MAX_WG * (d + 2); }

@@ -316,6 +316,24 @@ gp_status gp_lml_grad_matern_batched(gp_ctx *ctx, const double *X, int n, int d,
 /* L-BFGS on the first nparams hyper-parameters (m = history, maxIter = max_iter, best-seen point), as gp_optimize_rbf. */
 gp_status gp_optimize_matern(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int nu2, double sigma_noise, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out, int *evals_out);
 
+/* ---- kernel-matrix product without the matrix, mean-only prediction ---------------------------- */
+/* C = K(Xs, X; theta) A with K = buildKernelMatrix(kernel, X*, X) (utils/MatrixUtils.scala:44-55: m x n, never a noise term) evaluated
+ * tile by tile on the device and NEVER stored: O(m n (d + T)) work, O(m T) memory.  nu2 = 0: ARD-RBF, 3 / 5: ARD Matern 3/2 / 5/2,
+ * anything else GP_EINVAL; theta = (sf, l_1..l_d, sn), sn unused.  Xs is m x d (ldxs >= m), X n x d (ldx >= n), A n x T (lda >= n),
+ * C m x T (ldc >= m), all column-major; 1 <= d <= 64, else GP_EINVAL, as for bad leading dimensions.  m, n or T = 0: GP_OK, nothing
+ * written.  m and T are unbounded: rows and columns go through in batches whose scratch stays under 512 MiB.  Sums run in a fixed
+ * order (no atomics): the same inputs give the same bits.  The building block of matrix-free solvers and of multi-target means over
+ * shared inputs.  The _dev form takes device pointers and is asynchronous on the context's stream. */
+gp_status gp_kernel_matmul(gp_ctx *ctx, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta, const double *A, int T, int lda, double *C, int ldc);
+gp_status gp_kernel_matmul_dev(gp_ctx *ctx, int nu2, const double *dXs, int m, int ldxs, const double *dX, int n, int ldx, int d, const double *theta, const double *dA, int T, int lda, double *dC, int ldc);
+/* The posterior mean alone, mean = K* alpha (GpPredictor.scala:36), through the product above with T = 1: O(n d) per test point, no
+ * m x n workspace and no row solve -- gp_predict* with var = NULL still pays for both, and keeps its own results bit for bit.  For
+ * models from gp_fit_rbf*, gp_fit_matern* (appended and refitted ones included).  GP_EINVAL, with the reason in gp_last_error, for a model
+ * from gp_fit_co2, for one from gp_fit_from_gram, and for one whose last (re)fit failed (learnt as gp_predict_grad_dev learns it: one
+ * synchronisation after a refit).  m == 0: GP_OK, nothing written; m is unbounded. */
+gp_status gp_predict_mean(gp_model *model, const double *Xs, int m, int ldxs, double *mean);
+gp_status gp_predict_mean_dev(gp_model *model, const double *dXs, int m, int ldxs, double *dmean);   /* asynchronous */
+
 /* ---- leave-one-out cross-validation ------------------------------------------------------------ */
 /* Rasmussen & Williams, Gaussian Processes for Machine Learning, section 5.4.2, eqs. 5.10-5.13.  With kappa_i = [K^-1]_ii:
  *     mu_i = y_i - alpha_i / kappa_i,   sigma_i^2 = 1 / kappa_i                                                   (5.12)
