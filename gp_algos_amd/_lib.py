@@ -16,6 +16,7 @@ GP_PROF_OFF, GP_PROF_GEMM, GP_PROF_SYRK, GP_PROF_GRAM, GP_PROF_TRSM, GP_PROF_POT
 GP_EP_GET_L, GP_EP_GET_SIGMA, GP_EP_GET_MU, GP_EP_GET_CAV_TAU, GP_EP_GET_CAV_NU = range(5)
 GP_SMALL_GET_L, GP_SMALL_GET_LINV, GP_SMALL_GET_ALPHA = range(3)
 GP_SMALL_MAX_N = 2048
+GP_SS_E = {3: 8, 5: 16}    # nu2 -> steps per thread of the state-space scans (gpcore_internal.h gp_ss_e): a tile is 256 * E steps
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -103,6 +104,10 @@ SIGNATURES = {
     "gp_model_loo": (_i, [_vp, _dp, _dp, _dp]),
     "gp_loo_grad_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_loo": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),
+    "gp_ss_create": (_i, [_vp, _dp, _dp, _i, _i, C.POINTER(_vp)]),
+    "gp_ss_destroy": (None, [_vp]),
+    "gp_ss_lml": (_i, [_vp, _dp, _i, _dp, _ip]),
+    "gp_ss_predict": (_i, [_vp, _dp, _dp, _i, _dp, _dp, _dp]),
     "gp_small_fit":(_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
     "gp_small_from_factors": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_vp)]),
     "gp_small_fit_matern": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _i, _d, _i, C.POINTER(_vp), _ip]),

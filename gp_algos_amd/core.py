@@ -610,6 +610,54 @@ class RegressionModel:
         return mean, var, cov
 
 
+class StateSpaceModel:
+    """Matern 3/2 or 5/2 GP on 1-D inputs in its state-space form (gp_ss_*): the LML and the posterior of
+    RegressionModel(ctx, t[:, None], y, theta, kernel=...) in O(n) by Kalman filter and RTS smoother scans.  theta = (sf, l, sn)."""
+
+    def __init__(self, ctx, t, y, kernel="matern32"):
+        if kernel not in ("matern32", "matern52"):
+            raise ValueError("kernel must be 'matern32' or 'matern52'")
+        self.ctx = ctx
+        t, y = L.f64(np.asarray(t, dtype=np.float64).reshape(-1)), L.f64(np.asarray(y, dtype=np.float64).reshape(-1))
+        if y.size != t.size:
+            raise ValueError("Number of objects in training data matrix should be equal to targets vector length")
+        self.n = t.size
+        h = C.c_void_p()
+        ctx.check(ctx._lib.gp_ss_create(ctx.h, L.dptr(t), L.dptr(y), self.n, 3 if kernel == "matern32" else 5, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx._lib.gp_ss_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def lml_info(self, thetas):
+        """gp_ss_lml without raising: (status, lml[B], info[B]) -- a failed setting has NaN and the 1-based index of its observation."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64).reshape(-1, 3))
+        B = thetas.shape[0]
+        lml, info = np.zeros(B), np.zeros(B, dtype=np.int32)
+        st = self.ctx._lib.gp_ss_lml(self.h, L.dptr(thetas), B, L.dptr(lml), info.ctypes.data_as(C.POINTER(C.c_int)))
+        return st, lml, info
+
+    def lml(self, thetas):
+        """The LML at one setting (a float) or at B settings (B x 3 -> B values, one set of launches)."""
+        st, lml, info = self.lml_info(thetas)
+        self.ctx.check(st, int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0)
+        return float(lml[0]) if np.ndim(thetas) == 1 else lml
+
+    def predict(self, theta, ts):
+        """(mean[m], var[m], lml) at the test times ts, var = latent variance + sn^2 as RegressionModel.predict."""
+        theta, ts = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1)), L.f64(np.asarray(ts, dtype=np.float64).reshape(-1))
+        if theta.size != 3:
+            raise ValueError("%d does not equal to %d" % (theta.size, 3))
+        m = ts.size
+        mean, var, lml = np.zeros(m), np.zeros(m), np.zeros(1)
+        self.ctx.check(self.ctx._lib.gp_ss_predict(self.h, L.dptr(theta), L.dptr(ts), m, L.dptr(mean), L.dptr(var), L.dptr(lml)))
+        return mean, var, float(lml[0])
+
+
 class SmallModelBatch:
     """gp_small_*: G small GP models over ONE set of training inputs, resident with L^-1 (GP-UCB / GP-UKF workloads).
     kernel = "rbf" (ARD-RBF, the default), "matern32" or "matern52" (gp_small_fit_matern / gp_small_from_factors_matern); every

@@ -181,6 +181,21 @@ void gpk_loo_symv_lower(hipStream_t s, const double *A, int ld, int n, const dou
 void gpk_loo_mirror_scale(hipStream_t s, double *Kinv, int np, const double *c, double *S);
 // Q(i, j) -= alpha_i b_j + b_i alpha_j on the lower triangle, i < n
 void gpk_loo_weight(hipStream_t s, double *Q, int ld, int n, const double *alpha, const double *b);
+// State-space Matern GP on 1-D inputs (kernels_ss.hip): Kalman filter and RTS smoother as three-phase scans over tiles of 256 E steps.
+// steps per thread, chosen by measurement: 8 for nu = 3/2, 16 for nu = 5/2; GPCORE_SS_E overrides it per call (lab)
+constexpr int gp_ss_e(int nu2) { return nu2 == 3 ? 8 : 16; }
+int gpk_ss_tiles(int N, int E);
+struct gpk_ss_ws { double *agg = nullptr, *pre = nullptr, *part = nullptr; int *bad = nullptr; };    // tile aggregates, tile prefix states, LML / failure partials
+size_t gpk_ss_ws_doubles(int N, int E, int B);
+gpk_ss_ws gpk_ss_ws_carve(double *base, int N, int E, int B);
+// t, y: N steps in time order (device); src: nullptr = all observed, else src[k] < 0 marks test time -src[k] - 1; thetas: B x 3 (sf, l, sn) on the
+// device.  lml[B], info[B] (device): the LML or NaN, and 1 + the first step in time order whose innovation variance is not positive and finite
+// (0 = none).  fm / fP (B = 1 only; nullptr = not wanted): the filtered means (D x N) and packed covariances (D (D + 1) / 2 x N), D = (nu2 + 1) / 2
+void gpk_ss_filter(hipStream_t s, int nu2, const double *t, const double *y, const int *src, int N, int E, int B, const double *thetas, const gpk_ss_ws &w,
+                   double *lml, int *info, double *fm, double *fP);
+// mean / var[j] (device) of test time j = -src[k] - 1 from the filtered moments: smoothed mean, smoothed latent variance + sn^2
+void gpk_ss_smooth(hipStream_t s, int nu2, const double *t, const int *src, int N, int E, const double *theta, const double *fm, const double *fP,
+                   const gpk_ss_ws &w, double *mean, double *var);
 // Co2Kernel (gp/regression/Co2Prediction.scala:29-137), 1-D inputs, theta = hp1..hp11 on the host; pos = 0: kernel, 1..11: derivative
 void gpk_co2_gram(hipStream_t s, const double *xr, int nr, const double *xc, int nc, const double *theta, int pos, double *K, int ldk, int sym,
                   int full, double extra);

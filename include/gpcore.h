@@ -45,6 +45,7 @@ typedef struct gp_model gp_model; /* fitted regression model: X, L, alpha reside
 typedef struct gp_ep gp_ep;       /* EP classification state: K, Sigma, L, site parameters in HBM  */
 typedef struct gp_dist gp_dist;   /* RCCL communicator of one rank (one process per GPU)           */
 typedef struct gp_small gp_small; /* G small GP models over one set of training inputs (GP-UCB, GP-UKF) */
+typedef struct gp_ss gp_ss;       /* state-space Matern GP on 1-D inputs: times and targets in time order in HBM */
 
 /* ---- library / context ------------------------------------------------------------------- */
 const char *gp_version(void);
@@ -354,6 +355,29 @@ gp_status gp_model_loo(gp_model *model, double *mean, double *var, double *logp)
 gp_status gp_loo_grad_batched(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *thetas, int B, int nparams, int kernel, double sigma_noise, double *logp, double *grad, int *info);
 /* L-BFGS on the first nparams hyper-parameters maximising L_LOO (eqs. 5.10-5.13 through gp_loo_grad_batched), as gp_optimize_matern. */
 gp_status gp_optimize_loo(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int kernel, double sigma_noise, int max_iter, int history, double *theta_out, double *logp_out, int *iters_out, int *evals_out);
+
+/* ---- state-space Matern GP on 1-D inputs: O(n) LML and prediction ------------------------------- */
+/* For d = 1 the Matern 3/2 and 5/2 kernels are the covariance of the first component of a linear stochastic differential equation
+ * with a 2- or 3-dimensional state, so the posterior and the log marginal likelihood of gp_fit_matern / gp_predict on such data follow
+ * from a Kalman filter and a Rauch-Tung-Striebel smoother in O(n) instead of O(n^3) (Hartikainen & Sarkka, Kalman filtering and
+ * smoothing solutions to temporal Gaussian process regression models, 2010).  Both recursions run as associative scans (Sarkka &
+ * Garcia-Fernandez, Temporal parallelization of Bayesian smoothers, 2021), so n is bounded by memory alone (16 bytes per observation).
+ * theta = (sf, l, sn), the layout of an ARD Matern model with d = 1.  With lambda = sqrt(nu2) / l, H = (1, 0, ..):
+ *     nu2 = 3:  Pinf = diag(sf^2, lambda^2 sf^2),  A(D) = e^(-lambda D) [[1 + lambda D, D], [-lambda^2 D, 1 - lambda D]]
+ *     nu2 = 5:  Pinf = sf^2 [[1, 0, -k], [0, k, 0], [-k, 0, lambda^4]], k = lambda^2 / 3, A(D) = expm(F D) in closed form
+ *     Q(D) = Pinf - A(D) Pinf A(D)^T,  prior N(0, Pinf) at the first time,  y_k = H x_k + N(0, sn^2).
+ * gp_ss_create: t[n] finite in any order, duplicates allowed (sorted once, stably; the order is kept), y[n]; nu2 in {3, 5}. */
+gp_status gp_ss_create(gp_ctx *ctx, const double *t, const double *y, int n, int nu2, gp_ss **out);
+void gp_ss_destroy(gp_ss *ss);
+/* lml[b] = log p(y | t, theta_b) at B settings (thetas B x 3 row-major) in one set of launches; the same inputs give the same bits.
+ * A setting with an innovation variance that is not positive and finite (sn = 0 with a duplicated time, NaN in theta) gets lml[b] = NaN
+ * and info[b] = the 1-based index, in the caller's order, of the first such observation in time order; the others are unaffected
+ * (info[b] = 0) and the call returns GP_ENOTPD.  info may be NULL.  GP_EINVAL for sf <= 0 or l <= 0. */
+gp_status gp_ss_lml(gp_ss *ss, const double *thetas, int B, double *lml, int *info);
+/* Posterior at m test times ts[m] (finite, any order, may coincide with training times), in the caller's order: mean[m] and
+ * var[m] = latent variance + sn^2, gp_predict's var_diag convention, so both equal what gp_fit_matern + gp_predict return on the same
+ * data.  *lml (may be NULL) = the LML at theta.  GP_ENOTPD as for gp_ss_lml, with NaN in mean and var. */
+gp_status gp_ss_predict(gp_ss *ss, const double *theta, const double *ts, int m, double *mean, double *var, double *lml);
 
 /* ---- batched small-n posteriors: GP-UCB and GP-UKF --------------------------------------------- */
 /* The heaviest callers of GpPredictor.computePosterior (gp/regression/GpPredictor.scala:45-58) ask for ONE test point per call
