@@ -107,6 +107,8 @@ SIGNATURES = {
     "gp_ss_create": (_i, [_vp, _dp, _dp, _i, _i, C.POINTER(_vp)]),
     "gp_ss_destroy": (None, [_vp]),
     "gp_ss_lml": (_i, [_vp, _dp, _i, _dp, _ip]),
+    "gp_ss_lml_grad": (_i, [_vp, _dp, _i, _dp, _dp, _ip]),
+    "gp_ss_optimize": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _ip, _ip]),
     "gp_ss_predict": (_i, [_vp, _dp, _dp, _i, _dp, _dp, _dp]),
     "gp_small_fit":(_i, [_vp, _dp, _i, _i, _i, _dp, _i, _i, _dp, _d, _i, C.POINTER(_vp), _ip]),
     "gp_small_from_factors": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_vp)]),

@@ -611,8 +611,8 @@ class RegressionModel:
 
 
 class StateSpaceModel:
-    """Matern 3/2 or 5/2 GP on 1-D inputs in its state-space form (gp_ss_*): the LML and the posterior of
-    RegressionModel(ctx, t[:, None], y, theta, kernel=...) in O(n) by Kalman filter and RTS smoother scans.  theta = (sf, l, sn)."""
+    """Matern 3/2 or 5/2 GP on 1-D inputs in its state-space form (gp_ss_*): the LML, its gradient, the fit and the posterior of
+    RegressionModel(ctx, t[:, None], y, theta, kernel=...) in O(n) by Kalman filter, sensitivity and RTS smoother scans.  theta = (sf, l, sn)."""
 
     def __init__(self, ctx, t, y, kernel="matern32"):
         if kernel not in ("matern32", "matern52"):
@@ -646,6 +646,31 @@ class StateSpaceModel:
         st, lml, info = self.lml_info(thetas)
         self.ctx.check(st, int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0)
         return float(lml[0]) if np.ndim(thetas) == 1 else lml
+
+    def lml_grad_info(self, thetas):
+        """gp_ss_lml_grad without raising: (status, lml[B], grad[B, 3], info[B]) -- a failed setting has NaN in lml and grad."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64).reshape(-1, 3))
+        B = thetas.shape[0]
+        lml, grad, info = np.zeros(B), np.zeros((B, 3)), np.zeros(B, dtype=np.int32)
+        st = self.ctx._lib.gp_ss_lml_grad(self.h, L.dptr(thetas), B, L.dptr(lml), L.dptr(grad), info.ctypes.data_as(C.POINTER(C.c_int)))
+        return st, lml, grad, info
+
+    def lml_grad(self, thetas):
+        """The LML and dLML/d(sf, l, sn) at one setting (float, grad[3]) or at B settings (lml[B], grad[B, 3]; one set of launches)."""
+        st, lml, grad, info = self.lml_grad_info(thetas)
+        self.ctx.check(st, int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0)
+        return (float(lml[0]), grad[0]) if np.ndim(thetas) == 1 else (lml, grad)
+
+    def fit(self, theta0, nparams=3, max_iter=20, history=4):
+        """gp_ss_optimize: (theta*, LML(theta*), iterations, evaluations), L-BFGS on the first nparams of (sf, l, sn)."""
+        theta0 = L.f64(np.asarray(theta0, dtype=np.float64).reshape(-1))
+        if theta0.size != 3:
+            raise ValueError("%d does not equal to %d" % (theta0.size, 3))
+        out, lml = np.zeros(3), np.zeros(1)
+        its, evs = C.c_int(0), C.c_int(0)
+        self.ctx.check(self.ctx._lib.gp_ss_optimize(self.h, L.dptr(theta0), int(nparams), int(max_iter), int(history), L.dptr(out), L.dptr(lml),
+                                                    C.byref(its), C.byref(evs)))
+        return out, float(lml[0]), its.value, evs.value
 
     def predict(self, theta, ts):
         """(mean[m], var[m], lml) at the test times ts, var = latent variance + sn^2 as RegressionModel.predict."""

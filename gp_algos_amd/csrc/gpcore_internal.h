@@ -185,14 +185,21 @@ void gpk_loo_weight(hipStream_t s, double *Q, int ld, int n, const double *alpha
 // steps per thread, chosen by measurement: 8 for nu = 3/2, 16 for nu = 5/2; GPCORE_SS_E overrides it per call (lab)
 constexpr int gp_ss_e(int nu2) { return nu2 == 3 ? 8 : 16; }
 int gpk_ss_tiles(int N, int E);
-struct gpk_ss_ws { double *agg = nullptr, *pre = nullptr, *part = nullptr; int *bad = nullptr; };    // tile aggregates, tile prefix states, LML / failure partials
-size_t gpk_ss_ws_doubles(int N, int E, int B);
-gpk_ss_ws gpk_ss_ws_carve(double *base, int N, int E, int B);
+struct gpk_ss_ws {
+    double *agg = nullptr, *pre = nullptr, *part = nullptr; int *bad = nullptr;      // tile aggregates, tile prefix states, LML / failure partials
+    // gradient only: sensitivity aggregates and prefix states, v^2 / S and gradient partials per tile, start moments and local prefixes per thread
+    double *agg2 = nullptr, *pre2 = nullptr, *quad = nullptr, *gpart = nullptr, *start = nullptr, *lpre = nullptr;
+};
+size_t gpk_ss_ws_doubles(int N, int E, int B, bool grad = false);
+gpk_ss_ws gpk_ss_ws_carve(double *base, int N, int E, int B, bool grad = false);
 // t, y: N steps in time order (device); src: nullptr = all observed, else src[k] < 0 marks test time -src[k] - 1; thetas: B x 3 (sf, l, sn) on the
 // device.  lml[B], info[B] (device): the LML or NaN, and 1 + the first step in time order whose innovation variance is not positive and finite
 // (0 = none).  fm / fP (B = 1 only; nullptr = not wanted): the filtered means (D x N) and packed covariances (D (D + 1) / 2 x N), D = (nu2 + 1) / 2
 void gpk_ss_filter(hipStream_t s, int nu2, const double *t, const double *y, const int *src, int N, int E, int B, const double *thetas, const gpk_ss_ws &w,
                    double *lml, int *info, double *fm, double *fP);
+// The same lml and info (bit for bit) and grad[B x 3] (device) = dLML/d(sf, l, sn), NaN where info[b] != 0; every step observed; w carved with grad = true
+void gpk_ss_grad(hipStream_t s, int nu2, const double *t, const double *y, int N, int E, int B, const double *thetas, const gpk_ss_ws &w, double *lml, int *info,
+                 double *grad);
 // mean / var[j] (device) of test time j = -src[k] - 1 from the filtered moments: smoothed mean, smoothed latent variance + sn^2
 void gpk_ss_smooth(hipStream_t s, int nu2, const double *t, const int *src, int N, int E, const double *theta, const double *fm, const double *fP,
                    const gpk_ss_ws &w, double *mean, double *var);

@@ -1,5 +1,6 @@
 // C-ABI of the state-space Matern GP on 1-D inputs (kernels_ss.hip): gp_ss_create sorts the times once and keeps them on the device,
-// gp_ss_lml runs the filter scan for B settings in one set of launches, gp_ss_predict merges the test times into the time line as
+// gp_ss_lml runs the filter scan for B settings in one set of launches, gp_ss_lml_grad the filter and sensitivity scans, gp_ss_optimize
+// L-BFGS on that gradient, gp_ss_predict merges the test times into the time line as
 // unobserved steps and runs the filter scan (storing the filtered moments) and the smoother scan over the N = n + m steps.
 #include "gpcore_internal.h"
 
@@ -29,6 +30,43 @@ bool all_finite(const double *p, size_t count) {
 
 // (sf, l, sn): sf <= 0 or l <= 0 is a bad argument; NaN goes through and surfaces as a failed step
 bool theta_ok(const double *th) { return !(th[0] <= 0.0) && !(th[1] <= 0.0); }
+
+// gp_ss_lml_grad after its argument checks.  The per-thread records of the gradient path are 312 bytes per 256-th of a tile, so the
+// settings go through in groups whose workspace stays under 512 MiB (a group of one may exceed it); a setting's results do not depend
+// on its group.
+gp_status ss_lml_grad_run(gp_ss *ss, const double *thetas, int B, double *lml, double *grad, int *info) {
+    gp_ctx *ctx = ss->ctx;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    const int n = ss->n, E = ss_steps_per_thread(ss->nu2);
+    const size_t per = gpk_ss_ws_doubles(n, E, 1, true);
+    const int G = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, ((size_t)64 << 20) / per));
+    double *base = nullptr, *small = nullptr;
+    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * gpk_ss_ws_doubles(n, E, G, true), &base));
+    GP_TRY(gpi_ws_get(ctx, WS_SUMSQ, sizeof(double) * (size_t)8 * G, &small));       // thetas | lml | grad | info
+    double *dth = small, *dlml = small + 3 * (size_t)G, *dgrad = small + 4 * (size_t)G;
+    int *dinfo = reinterpret_cast<int *>(small + 7 * (size_t)G);
+    std::vector<int> h(G);
+    gp_status st = GP_OK;
+    for (int b0 = 0; b0 < B; b0 += G) {
+        const int g = std::min(G, B - b0);
+        const gpk_ss_ws w = gpk_ss_ws_carve(base, n, E, g, true);
+        GP_TRY(gpi_upload_2d(ctx, dth, 3 * g, thetas + 3 * (size_t)b0, 3 * g, 3 * g, 1));
+        gpk_ss_grad(ctx->stream, ss->nu2, ss->dt, ss->dy, n, E, g, dth, w, dlml, dinfo, dgrad);
+        GP_LAUNCH_CHECK(ctx);
+        GP_HIP(ctx, hipMemcpyAsync(h.data(), dinfo, sizeof(int) * g, hipMemcpyDeviceToHost, ctx->stream));
+        GP_TRY(gpi_download_2d(ctx, grad + 3 * (size_t)b0, 3 * g, dgrad, 3 * g, 3 * g, 1));
+        GP_TRY(gpi_download_2d(ctx, lml + b0, g, dlml, g, g, 1));                    // synchronises
+        for (int b = 0; b < g; ++b) {
+            const int at = h[b] ? ss->perm[h[b] - 1] + 1 : 0;
+            if (info) info[b0 + b] = at;
+            if (at && st == GP_OK) {
+                GP_SET_ERR(ctx, "innovation variance not positive and finite at observation %d (setting %d)", at, b0 + b);
+                st = GP_ENOTPD;
+            }
+        }
+    }
+    return st;
+}
 
 }  // namespace
 
@@ -98,6 +136,44 @@ gp_status gp_ss_lml(gp_ss *ss, const double *thetas, int B, double *lml, int *in
         }
     }
     return st;
+}
+
+gp_status gp_ss_lml_grad(gp_ss *ss, const double *thetas, int B, double *lml, double *grad, int *info) {
+    if (!ss) return GP_EINVAL;
+    gp_ctx *ctx = ss->ctx;
+    GP_REQUIRE(ctx, thetas && lml && grad && B >= 0, "null pointer or B < 0");
+    for (int b = 0; b < B; ++b) GP_REQUIRE(ctx, theta_ok(thetas + 3 * (size_t)b), "theta = (sf, l, sn) needs sf > 0 and l > 0");
+    if (B == 0) return GP_OK;
+    return ss_lml_grad_run(ss, thetas, B, lml, grad, info);
+}
+
+gp_status gp_ss_optimize(gp_ss *ss, const double *theta0, int nparams, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out,
+                         int *evals_out) {
+    if (!ss) return GP_EINVAL;
+    gp_ctx *ctx = ss->ctx;
+    GP_REQUIRE(ctx, theta0 && theta_out, "null pointer");
+    GP_REQUIRE(ctx, nparams >= 1 && nparams <= 3 && max_iter >= 0 && history >= 1, "bad arguments (1 <= nparams <= 3)");
+    GP_REQUIRE(ctx, theta_ok(theta0), "theta = (sf, l, sn) needs sf > 0 and l > 0");
+    constexpr int NC = 4;
+    // a trial step with sf <= 0 or l <= 0 is a failed setting (bad != 0, like a matrix that is not positive definite), not a bad argument
+    auto evaluate = [&](const double *thetas, int count, double *f, double *g, int *bad) -> gp_status {
+        std::vector<double> th, fl(count), gl(3 * (size_t)count);
+        std::vector<int> at, inf(count);
+        for (int c = 0; c < count; ++c) {
+            if (theta_ok(thetas + 3 * (size_t)c)) at.push_back(c), th.insert(th.end(), thetas + 3 * (size_t)c, thetas + 3 * (size_t)c + 3);
+            f[c] = NAN, bad[c] = 1;
+            for (int p = 0; p < nparams; ++p) g[(size_t)c * nparams + p] = NAN;
+        }
+        if (at.empty()) return GP_OK;
+        const gp_status st = ss_lml_grad_run(ss, th.data(), (int)at.size(), fl.data(), gl.data(), inf.data());
+        if (st != GP_OK && st != GP_ENOTPD) return st;
+        for (size_t i = 0; i < at.size(); ++i) {
+            f[at[i]] = fl[i], bad[at[i]] = inf[i];
+            for (int p = 0; p < nparams; ++p) g[(size_t)at[i] * nparams + p] = gl[3 * i + p];
+        }
+        return GP_OK;
+    };
+    return gpi_lbfgs_maximize(ctx, 3, nparams, theta0, max_iter, history, NC, evaluate, theta_out, lml_out, iters_out, evals_out);
 }
 
 gp_status gp_ss_predict(gp_ss *ss, const double *theta, const double *ts, int m, double *mean, double *var, double *lml) {

@@ -259,3 +259,139 @@ template <int D> struct ss_smooth {
         ss_pack<D>(X, v + OL);                                 // L = P - E A P
     }
 };
+
+// ---- LML gradient: the sensitivity of the filter --------------------------------------------------------------------------------------
+// d/dlambda of Pinf, A(dt) and Q(dt); A: ss_amat's.  dA = -dt A + e^(-x) d(polynomial part)/dlambda, with the two terms merged so that
+// small x cancels nothing; dQ = dPinf - dA Pinf A^T - A dPinf A^T - A Pinf dA^T, symmetrised as ss_trans does
+SS_FN void ss_dpinf(const ss_par &p, double (&P)[2][2]) { P[0][0] = P[0][1] = P[1][0] = 0.0, P[1][1] = 2.0 * p.lam * p.sf2; }
+SS_FN void ss_dpinf(const ss_par &p, double (&P)[3][3]) {
+    const double dk = 2.0 * p.lam / 3.0 * p.sf2;
+    P[0][0] = P[0][1] = P[1][0] = P[1][2] = P[2][1] = 0.0, P[0][2] = P[2][0] = -dk, P[1][1] = dk, P[2][2] = 4.0 * p.lam * p.lam * p.lam * p.sf2;
+}
+SS_FN void ss_damat(const ss_par &p, double dt, double (&A)[2][2]) {
+    const double x = p.lam * dt, e = exp(-x);
+    A[0][0] = -e * x * dt, A[0][1] = -e * dt * dt, A[1][0] = e * x * (x - 2.0), A[1][1] = e * dt * (x - 2.0);
+}
+SS_FN void ss_damat(const ss_par &p, double dt, double (&A)[3][3]) {
+    const double l = p.lam, x = l * dt, e = exp(-x), q = -0.5 * x * x + 3.0 * x - 3.0;
+    A[0][0] = -e * 0.5 * dt * x * x, A[0][1] = -e * dt * dt * x, A[0][2] = -e * 0.5 * dt * dt * dt;
+    A[1][0] = e * 0.5 * x * x * (x - 3.0), A[1][1] = e * dt * x * (x - 3.0), A[1][2] = e * 0.5 * dt * dt * (x - 3.0);
+    A[2][0] = e * l * x * q, A[2][1] = e * 2.0 * x * q,A[2][2] = e * dt * q;
+}
+template <int D> SS_FN void ss_dtrans(const ss_par &p, double dt, bool first, const double (&A)[D][D], double (&dA)[D][D], double (&dQ)[D][D]) {
+    double dPi[D][D];
+    ss_dpinf(p, dPi);
+    if (first) {
+        SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) dA[i][j] = 0.0, dQ[i][j] = dPi[i][j]; }
+        return;
+    }
+    double Pi[D][D], AP[D][D], Y[D][D], X[D][D], Z[D][D];
+    ss_pinf(p, Pi);
+    ss_damat(p, dt, dA);
+    ss_mm<D>(A, Pi, AP);
+    ss_mm_nt<D>(dA, AP, Y);                                    // dA Pinf A^T
+    ss_mm<D>(A, dPi, X);
+    ss_mm_nt<D>(X, A, Z);                                      // A dPinf A^T
+    SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) dQ[i][j] = dPi[i][j] - (Y[i][j] + Y[j][i]) - 0.5 * (Z[i][j] + Z[j][i]); }
+}
+
+// What one observed step with transition (A, Q) from the filtered moments (m, P) of the step before shares between the directions:
+// AP = A P, S = P^-_00 + R, rs = 1 / S, vs = v / S with v = y - (A m)_0, the gain K = P^- h / S
+template <int D> struct ss_gain { double AP[D][D], K[D], S, rs, v, vs; };
+template <int D> SS_FN void ss_make_gain(const double (&A)[D][D], const double (&Q)[D][D], const double (&m)[D], const double (&P)[D][D], double y, double R,
+                                         ss_gain<D> &w) {
+    double X[D][D], mp[D];
+    ss_mm<D>(A, P, w.AP);
+    ss_mm_nt<D>(w.AP, A, X);
+    ss_mv<D>(A, m, mp);
+    w.S = X[0][0] + Q[0][0] + R, w.rs = 1.0 / w.S, w.v = y - mp[0], w.vs = w.v * w.rs;
+    SS_UNROLL for (int i = 0; i < D; ++i) w.K[i] = (0.5 * (X[i][0] + X[0][i]) + Q[i][0]) * w.rs;
+}
+// F = dA P A^T + A P dA^T + dQ
+template <int D> SS_FN void ss_sens_forcing(const double (&dA)[D][D], const double (&dQ)[D][D], const ss_gain<D> &w, double (&F)[D][D]) {
+    double X[D][D];
+    ss_mm_nt<D>(dA, w.AP, X);
+    SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) F[i][j] = X[i][j] + X[j][i] + dQ[i][j]; }
+}
+// u -> J u and M -> J M J^T + K K^T dR for J = I - K h^T, M symmetric
+template <int D> SS_FN void ss_sens_project(const ss_gain<D> &w, double dR, double (&u)[D], double (&M)[D][D]) {
+    double JM[D][D];
+    const double u0 = u[0];
+    SS_UNROLL for (int i = 0; i < D; ++i) u[i] -= w.K[i] * u0;
+    SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) JM[i][j] = M[i][j] - w.K[i] * M[0][j]; }
+    SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) M[i][j] = JM[i][j] - JM[i][0] * w.K[j] + w.K[i] * w.K[j] * dR; }
+}
+
+// The derivatives (dm, dP) of the filtered moments in a direction obey dP_k = Phi dP_{k-1} Phi^T + L, dm_k = Phi dm_{k-1} + Phi dP_{k-1} a + g
+// with Phi = J A, a = A^T h v / S, L = J F J^T + K K^T dR, g = J (dA m + F h v / S) - K dR v / S: coefficients of the filter's trajectory
+// alone, and no inverse.  The coupling of dm to dP keeps the form Phi X a under composition, and (Phi, a) do not depend on the direction,
+// so ONE element carries both directions: (Phi, a, g_0, L_0, g_1, L_1), L packed.  Direction 0 is lambda (dA, dQ of ss_dtrans, dR = 0),
+// direction 1 is R = sn^2 (dA = dQ = 0, dR = 1); the chain rule to (l, sn) is applied to the finished sums.  a (x) b with a the earlier.
+// A prefix's (g_d, L_d) is (dm, dP) after its last step: all that a later step reads of it.
+template <int D> struct ss_sens {
+    static constexpr int NS = D * (D + 1) / 2, ND = 2, OP = 0, OA = D * D, OG = OA + D, NP = D + NS, NV = OG + ND * NP;
+    static constexpr int STATE = OG, NSTATE = ND * NP;
+    static SS_FN void identity(double (&v)[NV]) {
+        SS_UNROLL for (int i = 0; i < NV; ++i) v[i] = 0.0;
+        SS_UNROLL for (int i = 0; i < D; ++i) v[OP + i * D + i] = 1.0;
+    }
+    static SS_FN void op(const double (&x)[NV], const double (&z)[NV], double (&o)[NV]) {
+        double Px[D][D], Pz[D][D], Lx[D][D], Lz[D][D], X[D][D], Y[D][D], az[D], u[D], w[D];
+        ss_load<D>(x + OP, Px), ss_load<D>(z + OP, Pz);
+        SS_UNROLL for (int i = 0; i < D; ++i) az[i] = z[OA + i];
+        ss_mm<D>(Pz, Px, X);
+        ss_store<D>(X, o + OP);                                // Phi = Phi_z Phi_x
+        ss_mtv<D>(Px, az, u);
+        SS_UNROLL for (int i = 0; i < D; ++i) o[OA + i] = x[OA + i] + u[i];   // a = a_x + Phi_x^T a_z
+        SS_UNROLL for (int d = 0; d < ND; ++d) {
+            const int og = OG + d * NP, ol = og + D;
+            ss_unpack<D>(x + ol, Lx), ss_unpack<D>(z + ol, Lz);
+            ss_mv<D>(Lx, az, u);
+            SS_UNROLL for (int i = 0; i < D; ++i) u[i] += x[og + i];
+            ss_mv<D>(Pz, u, w);
+            SS_UNROLL for (int i = 0; i < D; ++i) o[og + i] = w[i] + z[og + i];          // g = Phi_z (g_x + L_x a_z) + g_z
+            ss_mm<D>(Pz, Lx, X);
+            ss_mm_nt<D>(X, Pz, Y);
+            SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) Y[i][j] += Lz[i][j]; }
+            ss_pack<D>(Y, o + ol);                             // L = Phi_z L_x Phi_z^T + L_z
+        }
+    }
+    // the element of one observed step from its transition and its derivative and the gain at the filtered moments (m, P) before it
+    static SS_FN void element(const double (&A)[D][D], const double (&dA)[D][D], const double (&dQ)[D][D], const double (&m)[D], const ss_gain<D> &w,
+                              double (&v)[NV]) {
+        double F[D][D], u[D];
+        SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) v[OP + i * D + j] = A[i][j] - w.K[i] * A[0][j]; }
+        SS_UNROLL for (int i = 0; i < D; ++i) v[OA + i] = A[0][i] * w.vs;
+        ss_sens_forcing<D>(dA, dQ, w, F);
+        ss_mv<D>(dA, m, u);
+        SS_UNROLL for (int i = 0; i < D; ++i) u[i] = fma(F[i][0], w.vs, u[i]);
+        ss_sens_project<D>(w, 0.0, u, F);
+        SS_UNROLL for (int i = 0; i < D; ++i) v[OG + i] = u[i];
+        ss_pack<D>(F, v + OG + D);
+        SS_UNROLL for (int i = 0; i < D; ++i) v[OG + NP + i] = -w.K[i] * w.vs;
+        SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = i; j < D; ++j) v[OG + NP + D + ss_sidx<D>(i, j)] = w.K[i] * w.K[j]; }
+    }
+};
+
+// One step of the sensitivity recursion in both directions, beside ss_kalman_step and BEFORE it (m, P: the filtered moments of the step
+// before): (dm, dP)[d] -> those of this step; dl[d] += the derivative of the step's LML term,
+//     -1/2 dS (1/S - v^2/S^2) + v (dA m + A dm)_0 / S,   dS = (A dP A^T + F)_00 + dR
+template <int D> SS_FN void ss_sens_step(const double (&A)[D][D], const double (&dA)[D][D], const double (&dQ)[D][D], const double (&m)[D],
+                                         const ss_gain<D> &w, double (&dm)[2][D], double (&dP)[2][D][D], double (&dl)[2]) {
+    double F[D][D], X[D][D], Y[D][D], u[D], dam[D];
+    ss_sens_forcing<D>(dA, dQ, w, F);
+    ss_mv<D>(dA, m, dam);
+    SS_UNROLL for (int d = 0; d < 2; ++d) {
+        const double dR = d == 0 ? 0.0 : 1.0;
+        ss_mv<D>(A, dm[d], u);
+        ss_mm<D>(A, dP[d], X);
+        ss_mm_nt<D>(X, A, Y);
+        SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = i; j < D; ++j) X[i][j] = X[j][i] = 0.5 * (Y[i][j] + Y[j][i]) + (d == 0 ? F[i][j] : 0.0); }
+        if (d == 0) { SS_UNROLL for (int i = 0; i < D; ++i) u[i] += dam[i]; }
+        dl[d] += fma(-0.5 * (X[0][0] + dR), w.rs - w.vs * w.vs, w.vs * u[0]);
+        SS_UNROLL for (int i = 0; i < D; ++i) u[i] = fma(X[i][0], w.vs, u[i]);
+        ss_sens_project<D>(w, dR, u, X);
+        SS_UNROLL for (int i = 0; i < D; ++i) dm[d][i] = u[i] - dR * w.K[i] * w.vs;
+        SS_UNROLL for (int i = 0; i < D; ++i) { SS_UNROLL for (int j = 0; j < D; ++j) dP[d][i][j] = X[i][j]; }
+    }
+}

@@ -356,7 +356,7 @@ gp_status gp_loo_grad_batched(gp_ctx *ctx, const double *X, int n, int d, int ld
 /* L-BFGS on the first nparams hyper-parameters maximising L_LOO (eqs. 5.10-5.13 through gp_loo_grad_batched), as gp_optimize_matern. */
 gp_status gp_optimize_loo(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta0, int nparams, int kernel, double sigma_noise, int max_iter, int history, double *theta_out, double *logp_out, int *iters_out, int *evals_out);
 
-/* ---- state-space Matern GP on 1-D inputs: O(n) LML and prediction ------------------------------- */
+/* ---- state-space Matern GP on 1-D inputs: O(n) LML, its gradient, fit and prediction ------------ */
 /* For d = 1 the Matern 3/2 and 5/2 kernels are the covariance of the first component of a linear stochastic differential equation
  * with a 2- or 3-dimensional state, so the posterior and the log marginal likelihood of gp_fit_matern / gp_predict on such data follow
  * from a Kalman filter and a Rauch-Tung-Striebel smoother in O(n) instead of O(n^3) (Hartikainen & Sarkka, Kalman filtering and
@@ -374,6 +374,27 @@ void gp_ss_destroy(gp_ss *ss);
  * and info[b] = the 1-based index, in the caller's order, of the first such observation in time order; the others are unaffected
  * (info[b] = 0) and the call returns GP_ENOTPD.  info may be NULL.  GP_EINVAL for sf <= 0 or l <= 0. */
 gp_status gp_ss_lml(gp_ss *ss, const double *thetas, int B, double *lml, int *info);
+/* The same lml[b] (bit for bit) and grad = dLML/d(sf, l, sn), B x 3 row-major: the layout of gp_lml_grad_matern_batched with d = 1.
+ * The Kalman filter's derivative in a direction p is an affine recursion whose coefficients are the filter's trajectory.  With
+ * P^- = A P A^T + Q, S = P^-_00 + R, v = y - (A m)_0, K = P^- h / S, J = I - K h^T, F = dA P A^T + A P dA^T + dQ (dA, dQ, dR: the
+ * derivatives of A, Q and R = sn^2; (m, P): the filtered moments of the step before):
+ *     dP_k = Phi dP_{k-1} Phi^T + L,    dm_k = Phi dm_{k-1} + Phi dP_{k-1} a + g,
+ *     Phi = J A,   a = A^T h v / S,   L = J F J^T + K K^T dR,   g = J (dA m + F h v / S) - K dR v / S,
+ *     dl_k = -1/2 dS (1/S - v^2/S^2) + v (dA m + A dm_{k-1})_0 / S,   dS = (A dP_{k-1} A^T + F)_00 + dR.
+ * The coupling of dm to dP keeps the form Phi X a under composition, so (Phi, a, g, L) is the element of ONE associative scan without an
+ * inverse: for x the earlier and z the later element
+ *     Phi = Phi_z Phi_x,  a = a_x + Phi_x^T a_z,  L = Phi_z L_x Phi_z^T + L_z,  g = Phi_z (g_x + L_x a_z) + g_z,   identity (I, 0, 0, 0).
+ * (Phi, a) do not depend on the direction: one element carries (g, L) of both directions, lambda = sqrt(nu2) / l (d/dl = (-lambda / l)
+ * d/dlambda; dA/dlambda, dPinf/dlambda in closed form, dQ = dPinf - dA Pinf A^T - A dPinf A^T - A Pinf dA^T) and R (d/dsn = 2 sn d/dR).
+ * The third comes from K = sf^2 (k_l + (sn / sf)^2 I):  sf dLML/dsf + sn dLML/dsn = sum_k v_k^2 / S_k - n.
+ * The sums run in a fixed order: the same inputs give the same bits, whatever the batch.  A failed setting gets NaN in lml[b] and all of
+ * grad[b] and info[b] as for gp_ss_lml; the batch goes on and the call returns GP_ENOTPD.  info may be NULL.  GP_EINVAL for sf <= 0 or
+ * l <= 0.  Settings are processed in groups that bound the workspace (39 doubles per 8 or 16 observations and setting). */
+gp_status gp_ss_lml_grad(gp_ss *ss, const double *thetas, int B, double *lml, double *grad, int *info);
+/* L-BFGS on the first nparams <= 3 of theta = (sf, l, sn) maximising the LML through gp_ss_lml_grad (m = history, maxIter = max_iter,
+ * best-seen point, the trial steps of an iteration as one batch), as gp_optimize_matern.  A trial step with sf <= 0 or l <= 0 counts as
+ * a failed setting; theta0 with sf <= 0 or l <= 0 is GP_EINVAL, one whose LML is undefined GP_ENOTPD. */
+gp_status gp_ss_optimize(gp_ss *ss, const double *theta0, int nparams, int max_iter, int history, double *theta_out, double *lml_out, int *iters_out, int *evals_out);
 /* Posterior at m test times ts[m] (finite, any order, may coincide with training times), in the caller's order: mean[m] and
  * var[m] = latent variance + sn^2, gp_predict's var_diag convention, so both equal what gp_fit_matern + gp_predict return on the same
  * data.  *lml (may be NULL) = the LML at theta.  GP_ENOTPD as for gp_ss_lml, with NaN in mean and var. */

@@ -1,7 +1,9 @@
-"""The state-space Matern GP (gp_ss_lml, gp_ss_predict) at time-series sizes, in one process: HIP events on the context's stream around
+"""The state-space Matern GP (gp_ss_lml, gp_ss_lml_grad, gp_ss_optimize, gp_ss_predict) at time-series sizes, in one process: HIP events on the context's stream around
 each call (wall clock beside them), one warm-up per shape, then the median of `--reps` calls.
   gp_ss_lml      n = 1e5, 1e6, 1e7, B = 1 and 16, both kernels: ns per step and setting, and the bytes the two filter passes must read
                  (t and y once per pass and setting: 32 bytes per step) per second
+  gp_ss_lml_grad the same shapes, right after gp_ss_lml in the same process: both times and their ratio
+  gp_ss_optimize B = 1 shapes, `--fit-iters` L-BFGS iterations from theta (each: one batch of 4 trial steps; 1 + 4 iterations evaluations)
   gp_ss_predict  n = 1e6, m = 1e5: filter passes (t, y and the source index, 20 bytes per step, read twice; the filtered moments written
                  once) and smoother passes (moments and t read twice, the source index once): 60 + 24 (D + D (D + 1) / 2) bytes per
                  step; the call includes the host's merge of the test times and its upload
@@ -26,6 +28,7 @@ ap.add_argument("--E", type=int, nargs="*", default=[])
 ap.add_argument("--predict", type=int, nargs=2, default=[1000000, 100000], metavar=("N", "M"))
 ap.add_argument("--dense", type=int, default=32768)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--fit-iters", type=int, default=5)
 a = ap.parse_args()
 THETA = np.array([1.3, 0.7, 0.05])
 stream = torch.cuda.Stream()
@@ -67,6 +70,14 @@ for n in a.n:
                 ms, wall = timed(lambda: ss.lml(thetas))
                 print("gp_ss_lml %s n=%d B=%d E=%d: %.3f ms (events) %.3f ms (wall)  %.3f ns per step and setting  %.1f GB/s of the 32 bytes per step"
                       % (kernel, n, B, E or L.GP_SS_E[nu2], ms, wall, ms * 1e6 / (n * B), 32.0 * n * B / (ms * 1e6)), flush=True)
+                gms, gwall = timed(lambda: ss.lml_grad(thetas))
+                print("gp_ss_lml_grad %s n=%d B=%d E=%d: %.3f ms (events) %.3f ms (wall)  %.3f ns per step and setting  %.2f x gp_ss_lml"
+                      % (kernel, n, B, E or L.GP_SS_E[nu2], gms, gwall, gms * 1e6 / (n * B), gms / ms), flush=True)
+            if not E and a.fit_iters:
+                res = []
+                fms, fwall = timed(lambda: res.append(ss.fit(THETA, max_iter=a.fit_iters)), min(a.reps, 3))
+                print("gp_ss_optimize %s n=%d max_iter=%d: %.3f ms (events) %.3f ms (wall)  %d iterations %d evaluations  lml %.6f -> %.6f"
+                      % (kernel, n, a.fit_iters, fms, fwall, res[-1][2], res[-1][3], ss.lml(THETA), res[-1][1]), flush=True)
             os.environ.pop("GPCORE_SS_E", None)
         ss.close()
 n, m = a.predict
