@@ -101,6 +101,14 @@ SIGNATURES = {
     "gp_kernel_matmul_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _dp, _vp, _i, _i, _vp, _i]),
     "gp_predict_mean": (_i, [_vp, _dp, _i, _i, _dp]),
     "gp_predict_mean_dev": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gp_kernel_syrk": (_i, [_vp, _i, _dp, _i, _i, _dp, _i, _i, _i, _dp, _dp, _dp, _i, _dp]),
+    "gp_kernel_syrk_dev": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _dp, _vp, _vp, _i, _vp]),
+    "gp_sparse_create": (_i, [_vp, _i, _dp, _i, _i, _i, _dp, _dp, _i, _i, _dp, _d, C.POINTER(_vp)]),
+    "gp_sparse_refit": (_i, [_vp, _dp]),
+    "gp_sparse_bound": (_i, [_vp, _dp]),
+    "gp_sparse_predict": (_i, [_vp, _dp, _i, _i, _dp, _dp]),
+    "gp_sparse_predict_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "gp_sparse_destroy": (None, [_vp]),
     "gp_model_loo": (_i, [_vp, _dp, _dp, _dp]),
     "gp_loo_grad_batched": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _i, _d, _dp, _dp, _ip]),
     "gp_optimize_loo": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _i, _d, _i, _i, _dp, _dp, _ip, _ip]),

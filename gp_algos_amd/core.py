@@ -313,6 +313,22 @@ class Context:
                                               L.dptr(Cm), max(m, 1)))
         return Cm[:, 0].copy() if vec else Cm
 
+    def kernel_syrk(self, Z, X, theta, y=None, kernel="rbf"):
+        """gp_kernel_syrk: (Phi, u) = (K(Z, X) K(X, Z), K(Z, X) y) with the M x n kernel matrix never stored; u is None without y."""
+        code = self._loo_kernel(kernel)
+        Z, X, theta = L.f64(Z), L.f64(X), L.f64(theta)
+        (M, d), n = Z.shape, X.shape[0]
+        if X.shape != (n, d) or theta.size != d + 2:
+            raise ValueError("dimension mismatch")
+        if y is not None:
+            y = L.f64(np.asarray(y, dtype=np.float64).reshape(-1))
+            if y.size != n:
+                raise ValueError("Number of objects in training data matrix should be equal to targets vector length")
+        Phi, u = np.zeros((M, M), order="F"), None if y is None else np.zeros(M)
+        self.check(self._lib.gp_kernel_syrk(self.h, code, L.dptr(Z), M, max(M, 1), L.dptr(X), n, max(n, 1), d, L.dptr(theta),
+                                            None if y is None else L.dptr(y), L.dptr(Phi), max(M, 1), None if y is None else L.dptr(u)))
+        return Phi, u
+
     def posterior_from_factor(self, X, theta, Lm, alpha, Xs, full_cov=False, want_v=False):
         """gp_posterior_from_factor (GpPredictor.computePosterior with the ARD-RBF kernel): (mean, var, cov|None, V|None)."""
         X, theta, Lm, alpha, Xs = L.f64(X), L.f64(theta), L.f64(Lm), L.f64(alpha), L.f64(Xs)
@@ -681,6 +697,59 @@ class StateSpaceModel:
         mean, var, lml = np.zeros(m), np.zeros(m), np.zeros(1)
         self.ctx.check(self.ctx._lib.gp_ss_predict(self.h, L.dptr(theta), L.dptr(ts), m, L.dptr(mean), L.dptr(var), L.dptr(lml)))
         return mean, var, float(lml[0])
+
+
+class SparseModel:
+    """Sparse GP regression on the inducing points Z (gp_sparse_*): Titsias' collapsed bound and the DTC predictions for n observations in
+    d dimensions at O(n M^2) through the fused kernel-Gram product, X and y resident on the device.  theta = (sf, l_1..l_d, sn), sn != 0;
+    jitter is relative (jitter sf^2 on the diagonal of K(Z, Z)).  A constructor or refit that raises NotPositiveDefinite leaves the model
+    unusable until a refit goes through."""
+
+    def __init__(self, ctx, X, y, Z, theta, kernel="rbf", jitter=1e-6):
+        self.ctx = ctx
+        code = Context._loo_kernel(kernel)
+        X, Z, theta = L.f64(X), L.f64(Z), L.f64(np.asarray(theta, dtype=np.float64).reshape(-1))
+        y = L.f64(np.asarray(y, dtype=np.float64).reshape(-1))
+        (self.n, self.d), self.M = X.shape, Z.shape[0]
+        if y.size != self.n:
+            raise ValueError("Number of objects in training data matrix should be equal to targets vector length")
+        if Z.shape != (self.M, self.d) or theta.size != self.d + 2:
+            raise ValueError("dimension mismatch")
+        h = C.c_void_p()
+        st = ctx._lib.gp_sparse_create(ctx.h, code, L.dptr(X), self.n, max(self.n, 1), self.d, L.dptr(y), L.dptr(Z), self.M, max(self.M, 1),
+                                       L.dptr(theta), float(jitter), C.byref(h))
+        self.h = h if h.value else None
+        ctx.check(st)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx._lib.gp_sparse_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def refit(self, theta):
+        """New hyper-parameters, same X, y and Z."""
+        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1))
+        if theta.size != self.d + 2:
+            raise ValueError("%d does not equal to %d" % (theta.size, self.d + 2))
+        self.ctx.check(self.ctx._lib.gp_sparse_refit(self.h, L.dptr(theta)))
+
+    def bound(self):
+        """The collapsed variational lower bound F <= log p(y | X, theta)."""
+        F = np.zeros(1)
+        self.ctx.check(self.ctx._lib.gp_sparse_bound(self.h, L.dptr(F)))
+        return float(F[0])
+
+    def predict(self, Xs, return_var=True):
+        """(mean[m], var[m]) at the rows of Xs, var = latent variance + sn^2 as RegressionModel.predict; return_var=False: the mean alone."""
+        Xs = L.f64(Xs)
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise ValueError("dimension mismatch")
+        m = Xs.shape[0]
+        mean, var = np.zeros(m), np.zeros(m) if return_var else None
+        self.ctx.check(self.ctx._lib.gp_sparse_predict(self.h, L.dptr(Xs), m, max(m, 1), L.dptr(mean), L.dptr(var) if return_var else None))
+        return (mean, var) if return_var else mean
 
 
 class SmallModelBatch:

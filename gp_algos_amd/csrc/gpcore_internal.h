@@ -167,6 +167,12 @@ void gpk_matern_far_scan(hipStream_t s, int nu2, const double *Xa, int na, int l
 size_t gpk_kernel_matmul_partials(int m, int n, int d, int T);
 void gpk_kernel_matmul(hipStream_t s, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta,
                        const double *center, const double *A, int T, int lda, double *partials, double *C, int ldc, int *far_flag);
+// Kernel-Gram product without the kernel matrix (kernels_ksyrk.hip): Phi (M x M, ldphi, both triangles) = K(Z, X) K(X, Z) and, with y and u
+// given, u[M] = K(Z, X) y, for the cross-Gram K(Z, X; theta) of Z (M x d) and X (n x d), never stored.  center, far_flag as for
+// gpk_kernel_matmul; partials: gpk_kernel_syrk_partials(M, n, d) doubles of scratch.  M, n >= 1.
+size_t gpk_kernel_syrk_partials(int M, int n, int d);
+void gpk_kernel_syrk(hipStream_t s, int nu2, const double *Z, int M, int ldz, const double *X, int n, int ldx, int d, const double *theta,
+                     const double *center, const double *y, double *partials, double *Phi, int ldphi, double *u, int *far_flag);
 // Leave-one-out cross-validation (kernels_loo.hip; Rasmussen & Williams eqs. 5.10-5.13).  np: the padded size, a multiple of GP_NB.
 constexpr int GP_LOO_CHUNKS = 16;     // column chunks of gpk_loo_diag and of the row part of gpk_loo_symv_lower
 // partial[GP_LOO_CHUNKS x np]: chunk sums of kappa_i = sum_{j >= i} T(i, j)^2 for the upper-triangular T = L^-T (np x np, ld = np)

@@ -46,6 +46,7 @@ typedef struct gp_ep gp_ep;       /* EP classification state: K, Sigma, L, site 
 typedef struct gp_dist gp_dist;   /* RCCL communicator of one rank (one process per GPU)           */
 typedef struct gp_small gp_small; /* G small GP models over one set of training inputs (GP-UCB, GP-UKF) */
 typedef struct gp_ss gp_ss;       /* state-space Matern GP on 1-D inputs: times and targets in time order in HBM */
+typedef struct gp_sparse gp_sparse; /* sparse GP on inducing points: X, y, Z and the M x M factors in HBM        */
 
 /* ---- library / context ------------------------------------------------------------------- */
 const char *gp_version(void);
@@ -334,6 +335,36 @@ gp_status gp_kernel_matmul_dev(gp_ctx *ctx, int nu2, const double *dXs, int m, i
  * synchronisation after a refit).  m == 0: GP_OK, nothing written; m is unbounded. */
 gp_status gp_predict_mean(gp_model *model, const double *Xs, int m, int ldxs, double *mean);
 gp_status gp_predict_mean_dev(gp_model *model, const double *dXs, int m, int ldxs, double *dmean);   /* asynchronous */
+
+/* ---- sparse GP regression on inducing points --------------------------------------------------- */
+/* The kernel-Gram product Phi = K(Z, X) K(X, Z) (M x M, ldphi >= M, both triangles, exactly symmetric) and u = K(Z, X) y (M), with the
+ * M x n cross-Gram K(Z, X; theta) evaluated tile by tile and NEVER stored: O(n M (M + d)) work, O(M^2) memory, one pass over the n
+ * observations.  nu2, theta and the layouts as for gp_kernel_matmul; Z is M x d (ldz >= M), X n x d (ldx >= n).  y and u go together and
+ * may both be NULL (Phi alone).  1 <= M <= 8192, n >= 1, 1 <= d <= 64, else GP_EINVAL.  Sums run in a fixed order: the same inputs
+ * give the same bits.  The _dev form takes device pointers and is asynchronous on the context's stream. */
+gp_status gp_kernel_syrk(gp_ctx *ctx, int nu2, const double *Z, int M, int ldz, const double *X, int n, int ldx, int d, const double *theta, const double *y, double *Phi, int ldphi, double *u);
+gp_status gp_kernel_syrk_dev(gp_ctx *ctx, int nu2, const double *dZ, int M, int ldz, const double *dX, int n, int ldx, int d, const double *theta, const double *dy, double *dPhi, int ldphi, double *du);
+/* Sparse GP regression on M << n inducing points Z that the caller chooses (Titsias, Variational learning of inducing variables in
+ * sparse Gaussian processes, 2009: the collapsed bound; DTC predictive equations), for d-dimensional inputs and n bounded by memory
+ * alone: X and y stay on the device, everything else is O(M^2).  With Kuu = K(Z, Z) + jitter sf^2 I = Lu Lu^T (jitter is RELATIVE),
+ * Phi and u as above, C = Lu^-1 Phi Lu^-T, B = I + C / sn^2 = LB LB^T, c = LB^-1 Lu^-1 u / sn:
+ *     F = -n/2 log 2 pi - (log|B| + n log sn^2) / 2 - (y^T y / sn^2 - c^T c) / 2 - (n sf^2 - tr C) / (2 sn^2)   <=  log p(y | X, theta),
+ *     mean* = K(X*, Z) Lu^-T LB^-T c / sn,    var* = sf^2 - |Lu^-1 k*|^2 + |LB^-1 Lu^-1 k*|^2 + sn^2.
+ * var INCLUDES the noise sn^2, as gp_predict's var_diag does.  Phi is built first so that the O(n M^2) work is one fused pass; its
+ * rounding is then amplified by 1 / lambda_min(Kuu): the relative error of F grows like 1 / jitter (about 1e-9 at jitter 1e-6, up to 5e-6
+ * at 1e-8 for d = 1), so keep jitter near 1e-6.
+ * gp_sparse_create: nu2 = 0 / 3 / 5, theta = (sf, l_1..l_d, sn) with sn != 0, 1 <= M <= 8192, n >= 1 (n < M is legal), 1 <= d <= 64,
+ * jitter >= 0, else GP_EINVAL.  A factorisation that meets a pivot that is not positive (duplicated inducing points with jitter = 0)
+ * gives GP_ENOTPD, with the matrix (Kuu or B) and the pivot in gp_last_error; the handle is still returned and is unusable -- gp_sparse_bound
+ * and gp_sparse_predict* return GP_EINVAL -- until a gp_sparse_refit goes through.  gp_sparse_refit: new theta (d + 2), same X, y, Z.  Both
+ * synchronise.  gp_sparse_predict*: mean[m] required, var[m] optional (NULL); m == 0: GP_OK, nothing written; the _dev form is
+ * asynchronous.  The gradient of F and the choice of Z are the caller's. */
+gp_status gp_sparse_create(gp_ctx *ctx, int nu2, const double *X, int n, int ldx, int d, const double *y, const double *Z, int M, int ldz, const double *theta, double jitter, gp_sparse **out);
+gp_status gp_sparse_refit(gp_sparse *sp, const double *theta);
+gp_status gp_sparse_bound(gp_sparse *sp, double *F);
+gp_status gp_sparse_predict(gp_sparse *sp, const double *Xs, int m, int ldxs, double *mean, double *var);
+gp_status gp_sparse_predict_dev(gp_sparse *sp, const double *dXs, int m, int ldxs, double *dmean, double *dvar);
+void gp_sparse_destroy(gp_sparse *sp);
 
 /* ---- leave-one-out cross-validation ------------------------------------------------------------ */
 /* Rasmussen & Williams, Gaussian Processes for Machine Learning, section 5.4.2, eqs. 5.10-5.13.  With kappa_i = [K^-1]_ii:
