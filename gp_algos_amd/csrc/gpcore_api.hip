@@ -160,6 +160,86 @@ const double *gpi_model_alpha_dev(gp_model *m) {
     return m->dalpha;
 }
 
+void gpi_model_kinv(gp_model *m, double *T, double *Kinv) {
+    const int np = m->np;
+    gpi_inverse_transpose_lower(m->ctx, T, m->dL, np, m->ldl, m->ddinv);                    // T = L^-T
+    gpk_gemm_nt(m->ctx->stream, np, np, np, 1.0, T, np, T, np, 0.0, Kinv, np, 1, 1);         // K^-1 = T T^T (lower)
+}
+
+void gpi_model_gram_sym(gp_model *m, const double *X, int n, int ldx, double *K, int ldk, int full, double extra_diag, bool own_center) {
+    gp_ctx *ctx = m->ctx;
+    if (m->kind == 1) gpk_co2_gram(ctx->stream, X, n, X, n, m->theta.data(), 0, K, ldk, 1, full, extra_diag);
+    else gpk_ard_gram_sym(ctx->stream, gp_nu2_of_kind(m->kind), X, n, m->d, ldx, m->theta.data(), K, ldk, full, extra_diag, gp_gram_flag(ctx),
+                          own_center ? m->dcen : nullptr);
+}
+
+void gpi_model_gram_cross(gp_model *m, const double *Xs, int rows, int ldxs, double *Ks, int ldks) {
+    gp_ctx *ctx = m->ctx;
+    if (m->kind == 1) gpk_co2_gram(ctx->stream, Xs, rows, m->dX, m->n, m->theta.data(), 0, Ks, ldks, 0, 1, 0.0);
+    else gpk_ard_gram_cross(ctx->stream, gp_nu2_of_kind(m->kind), Xs, rows, ldxs, m->dX, m->n, m->ldx, m->d, m->theta.data(), Ks, ldks, gp_gram_flag(ctx),
+                            m->dcen);
+}
+
+// A model of `kind` with X and y in place (from the host, or from device memory with a leading dimension) and, but for the Co2Kernel,
+// the centroid of X; not fitted yet
+static gp_status model_load(gp_ctx *ctx, int kind, const double *X, int n, int d, int ldx, const double *y, bool on_device, gp_model **out) {
+    gp_model *m = nullptr;
+    GP_TRY(gpi_model_alloc(ctx, n, d, true, &m));
+    m->kind = kind;
+    gp_status st = GP_OK;
+    if (on_device) gpk_copy_2d(ctx->stream, m->dX, n, X, ldx, n, d);
+    else st = gpi_upload_2d(ctx, m->dX, n, X, ldx, n, d);
+    if (st == GP_OK && kind != 1) gpk_centroid(ctx->stream, m->dX, n, d, n, m->dcen);
+    if (st == GP_OK && on_device) {
+        hipError_t e = hipMemcpyAsync(m->dy, y, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) { GP_SET_ERR(ctx, "copy y: %s", hipGetErrorString(e)); st = GP_EHIP; }
+    } else if (st == GP_OK) {
+        st = gpi_upload_2d(ctx, m->dy, n, y, n, n, 1);
+    }
+    if (st != GP_OK) { gp_model_destroy(m); return st; }
+    *out = m;
+    return GP_OK;
+}
+
+gp_status gpi_fit(gp_ctx *ctx, int kind, const double *X, int n, int d, int ldx, const double *y, bool on_device, const double *theta,
+                  double sigma_noise, gp_model **out, int *info) {
+    gp_model *m = nullptr;
+    GP_TRY(model_load(ctx, kind, X, n, d, ldx, y, on_device, &m));
+    gp_status st = gp_model_refit_dev(m, theta, sigma_noise);
+    if (st == GP_OK) st = gp_model_status(m, info);
+    if (st != GP_OK) { gp_model_destroy(m); return st; }
+    *out = m;
+    return GP_OK;
+}
+
+gp_status gpi_objective_batched(gp_ctx *ctx, int kind, const double *X, int n, int d, int ldx, const double *y, const double *thetas, int B, int P,
+                                int nparams, double sigma_noise, double *f, double *grad, int *info, const gpi_objective &objective) {
+    gp_model *m = nullptr;
+    gp_status st = model_load(ctx, kind, X, n, d, ldx, y, false, &m);
+    for (int b = 0; b < B && st == GP_OK; ++b) {
+        const double *th = thetas + (size_t)b * P;
+        st = gp_model_refit_dev(m, th, sigma_noise);
+        int h = 0;
+        if (st == GP_OK) st = gp_model_status(m, &h);
+        if (info) info[b] = h;
+        if (st == GP_ENOTPD) {   // this setting only: NaN results, go on
+            f[b] = NAN;
+            for (int p = 0; p < nparams; ++p) grad[(size_t)b * nparams + p] = NAN;
+            st = GP_OK;
+            continue;
+        }
+        if (st != GP_OK) break;
+        const double *f_dev = nullptr, *g_dev = nullptr;
+        st = objective(m, th, &f_dev, &g_dev);
+        if (st != GP_OK) break;
+        { hipError_t e = hipGetLastError(); if (e != hipSuccess) { GP_SET_ERR(ctx, "launch failed: %s", hipGetErrorString(e)); st = GP_EHIP; break; } }
+        st = gpi_download_2d(ctx, f + b, 1, f_dev, 1, 1, 1);
+        if (st == GP_OK) st = gpi_download_2d(ctx, grad + (size_t)b * nparams, nparams, g_dev, nparams, nparams, 1);
+    }
+    gp_model_destroy(m);
+    return st;
+}
+
 // A stream whose work stays off `reserved` of the device's CUs (0, or a device of fewer than 64 CUs: no mask); a plain stream where
 // the masked one cannot be made.
 static hipError_t masked_stream_create(hipStream_t *sp, int num_cu, int reserved) {
@@ -390,21 +470,21 @@ gp_status gp_hp_get_at_position(const double *theta, int d, int pos, double *out
     return GP_OK;
 }
 
+}  // extern "C"
+
 // ---- Gram ---------------------------------------------------------------------------------------
-gp_status gp_gram_rbf_dev(gp_ctx *ctx, const double *dX, int n, int d, int ldx, const double *theta, double *dK, int ldk, int uplo) {
-    if (!ctx) return GP_EINVAL;
+gp_status gpi_gram_dev(gp_ctx *ctx, int nu2, const double *dX, int n, int d, int ldx, const double *theta, double *dK, int ldk, int uplo) {
     GP_REQUIRE(ctx, dX && theta && dK, "null pointer");
     GP_REQUIRE(ctx, n >= 0 && d >= 1 && d <= 64 && ldx >= n && ldk >= n, "bad dimensions (1 <= d <= 64)");
     if (n == 0) return GP_OK;
     gp_prof_begin(ctx, GP_PROF_GRAM);
     // (one-shot call: the first point as centre, no extra launch; a fitted model and the batched paths use the centroid, computed once)
-    gpk_gram_sym(ctx->stream, dX, n, d, ldx, theta, dK, ldk, uplo == GP_FULL, 0.0, gp_gram_flag(ctx));
+    gpk_ard_gram_sym(ctx->stream, nu2, dX, n, d, ldx, theta, dK, ldk, uplo == GP_FULL, 0.0, gp_gram_flag(ctx));
     gp_prof_end(ctx, GP_PROF_GRAM, uplo == GP_FULL ? 8.0 * n * (double)n + 8.0 * n * d : 8.0 * n * (n + 1.0) / 2.0 + 8.0 * n * d);
     return GP_OK;
 }
 
-gp_status gp_gram_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *theta, double *K, int ldk, int uplo) {
-    if (!ctx) return GP_EINVAL;
+gp_status gpi_gram_host(gp_ctx *ctx, int nu2, const double *X, int n, int d, int ldx, const double *theta, double *K, int ldk, int uplo) {
     GP_REQUIRE(ctx, X && theta && K, "null pointer");
     GP_REQUIRE(ctx, n >= 0 && d >= 1 && d <= 64 && ldx >= n && ldk >= n, "bad dimensions (1 <= d <= 64)");
     if (n == 0) return GP_OK;
@@ -414,8 +494,34 @@ gp_status gp_gram_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const
     GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)n * n, &dK));
     GP_TRY(gpi_upload_2d(ctx, dX, n, X, ldx, n, d));
     if (uplo != GP_FULL) GP_TRY(gpi_upload_2d(ctx, dK, n, K, ldk, n, n));  // keep the caller's strict upper triangle
-    GP_TRY(gp_gram_rbf_dev(ctx, dX, n, d, n, theta, dK, n, uplo));
+    GP_TRY(gpi_gram_dev(ctx, nu2, dX, n, d, n, theta, dK, n, uplo));
     return gpi_download_2d(ctx, K, ldk, dK, n, n, n);
+}
+
+gp_status gpi_cross_gram_host(gp_ctx *ctx, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta,
+                              double *Ks, int ldks) {
+    GP_REQUIRE(ctx, Xs && X && theta && Ks, "null pointer");
+    GP_REQUIRE(ctx, m >= 0 && n >= 0 && d >= 1 && d <= 64 && ldxs >= m && ldx >= n && ldks >= m, "bad dimensions (1 <= d <= 64)");
+    if (m == 0 || n == 0) return GP_OK;
+    GP_HIP(ctx, hipSetDevice(ctx->device));
+    double *dXs, *dX, *dK;
+    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * d, &dXs));
+    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)n * d, &dX));
+    GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)m * n, &dK));
+    GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, d));
+    GP_TRY(gpi_upload_2d(ctx, dX, n, X, ldx, n, d));
+    gpk_ard_gram_cross(ctx->stream, nu2, dXs, m, m, dX, n, n, d, theta, dK, m, gp_gram_flag(ctx));
+    return gpi_download_2d(ctx, Ks, ldks, dK, m, m, n);
+}
+
+extern "C" {
+
+gp_status gp_gram_rbf_dev(gp_ctx *ctx, const double *dX, int n, int d, int ldx, const double *theta, double *dK, int ldk, int uplo) {
+    return ctx ? gpi_gram_dev(ctx, 0, dX, n, d, ldx, theta, dK, ldk, uplo) : GP_EINVAL;
+}
+
+gp_status gp_gram_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *theta, double *K, int ldk, int uplo) {
+    return ctx ? gpi_gram_host(ctx, 0, X, n, d, ldx, theta, K, ldk, uplo) : GP_EINVAL;
 }
 
 gp_status gp_dgram_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *theta, int pos, double *D, int ldd) {
@@ -436,19 +542,7 @@ gp_status gp_dgram_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, cons
 }
 
 gp_status gp_cross_gram_rbf(gp_ctx *ctx, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta, double *Ks, int ldks) {
-    if (!ctx) return GP_EINVAL;
-    GP_REQUIRE(ctx, Xs && X && theta && Ks, "null pointer");
-    GP_REQUIRE(ctx, m >= 0 && n >= 0 && d >= 1 && d <= 64 && ldxs >= m && ldx >= n && ldks >= m, "bad dimensions (1 <= d <= 64)");
-    if (m == 0 || n == 0) return GP_OK;
-    GP_HIP(ctx, hipSetDevice(ctx->device));
-    double *dXs, *dX, *dK;
-    GP_TRY(gpi_ws_get(ctx, WS_A, sizeof(double) * (size_t)m * d, &dXs));
-    GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * (size_t)n * d, &dX));
-    GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)m * n, &dK));
-    GP_TRY(gpi_upload_2d(ctx, dXs, m, Xs, ldxs, m, d));
-    GP_TRY(gpi_upload_2d(ctx, dX, n, X, ldx, n, d));
-    gpk_gram_cross(ctx->stream, dXs, m, m, dX, n, n, d, theta, dK, m, gp_gram_flag(ctx));
-    return gpi_download_2d(ctx, Ks, ldks, dK, m, m, n);
+    return ctx ? gpi_cross_gram_host(ctx, 0, Xs, m, ldxs, X, n, ldx, d, theta, Ks, ldks) : GP_EINVAL;
 }
 
 // ---- factorisation / solves ---------------------------------------------------------------------
@@ -499,9 +593,7 @@ gp_status gp_model_refit_dev(gp_model *m, const double *theta, double sigma_nois
     m->theta.assign(theta, theta + (m->kind == 1 ? 11 : m->d + 2));
     m->sigma_noise = sigma_noise;
     gp_prof_begin(ctx, GP_PROF_GRAM);
-    if (m->kind == 1) gpk_co2_gram(ctx->stream, m->dX, m->n, m->dX, m->n, theta, 0, m->dL, m->ldl, 1, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise);
-    else if (m->kind >= 2) gpk_matern_gram_sym(ctx->stream, m->dX, m->n, m->d, m->ldx, theta, 2 * m->kind - 1, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
-    else gpk_gram_sym(ctx->stream, m->dX, m->n, m->d, m->ldx, theta, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, gp_gram_flag(ctx), m->dcen);
+    gpi_model_gram_sym(m, m->dX, m->n, m->ldx, m->dL, m->ldl, 0, std::isnan(sigma_noise) ? 0.0 : sigma_noise, true);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m->n * (m->n + 1.0) / 2.0 + 8.0 * m->n * m->d);
     model_factor(m);
     GP_LAUNCH_CHECK(ctx);
@@ -523,20 +615,11 @@ gp_status gp_model_status(gp_model *m, int *info) {
 gp_status gp_fit_rbf_dev(gp_ctx *ctx, const double *dX, int n, int d, int ldx, const double *dy, const double *theta, double sigma_noise, gp_model **out, int *info) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
+    if (info) *info = 0;
     GP_REQUIRE(ctx, dX && dy && theta, "null pointer");
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && ldx >= n, "bad dimensions (n >= 1, 1 <= d <= 64)");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    gp_model *m = nullptr;
-    GP_TRY(gpi_model_alloc(ctx, n, d, true, &m));
-    gpk_copy_2d(ctx->stream, m->dX, n, dX, ldx, n, d);
-    gpk_centroid(ctx->stream, m->dX, n, d, n, m->dcen);
-    hipError_t e = hipMemcpyAsync(m->dy, dy, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) { gp_model_destroy(m); GP_SET_ERR(ctx, "copy y: %s", hipGetErrorString(e)); return GP_EHIP; }
-    gp_status st = gp_model_refit_dev(m, theta, sigma_noise);
-    if (st == GP_OK) st = gp_model_status(m, info);
-    if (st != GP_OK) { gp_model_destroy(m); return st; }
-    *out = m;
-    return GP_OK;
+    return gpi_fit(ctx, 0, dX, n, d, ldx, dy, true, theta, sigma_noise, out, info);
 }
 
 gp_status gp_fit_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const double *y, const double *theta, double sigma_noise, gp_model **out, int *info) {
@@ -546,16 +629,7 @@ gp_status gp_fit_rbf(gp_ctx *ctx, const double *X, int n, int d, int ldx, const 
     GP_REQUIRE(ctx, X && y && theta, "null pointer");
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && ldx >= n, "bad dimensions (n >= 1, 1 <= d <= 64)");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    gp_model *m = nullptr;
-    GP_TRY(gpi_model_alloc(ctx, n, d, true, &m));
-    gp_status st = gpi_upload_2d(ctx, m->dX, n, X, ldx, n, d);
-    if (st == GP_OK) gpk_centroid(ctx->stream, m->dX, n, d, n, m->dcen);
-    if (st == GP_OK) st = gpi_upload_2d(ctx, m->dy, n, y, n, n, 1);
-    if (st == GP_OK) st = gp_model_refit_dev(m, theta, sigma_noise);
-    if (st == GP_OK) st = gp_model_status(m, info);
-    if (st != GP_OK) { gp_model_destroy(m); return st; }
-    *out = m;
-    return GP_OK;
+    return gpi_fit(ctx, 0, X, n, d, ldx, y, false, theta, sigma_noise, out, info);
 }
 
 gp_status gp_fit_from_gram(gp_ctx *ctx, const double *K, int n, int ldk, const double *y, gp_model **out, int *info) {
@@ -611,10 +685,7 @@ gp_status gp_lml_grad_from_gram(gp_ctx *ctx, const double *K, int n, int ldk, co
         if (st == GP_OK) st = gpi_ws_get(ctx, WS_C, sizeof(double) * ((size_t)2 * np + nparams), &small);   // alpha | partial | g[nparams]
         double *alpha = small, *partial = small + np, *g = partial + np;
         if (st == GP_OK) st = gpi_model_alpha(m, alpha);
-        if (st == GP_OK) {
-            gpi_inverse_transpose_lower(ctx, T, m->dL, np, m->ldl, m->ddinv);                           // T = L^-T
-            gpk_gemm_nt(s, np, np, np, 1.0, T, np, T, np, 0.0, Kinv, np, 1, 1);                      // K^-1 = T T^T (lower)
-        }
+        if (st == GP_OK) gpi_model_kinv(m, T, Kinv);
         for (int p = 0; p < nparams && st == GP_OK; ++p) {
             st = gpi_upload_2d(ctx, D, np, dK[p], lddk, n, n);        // stream-ordered: the trace of p - 1 has read D before this lands
             if (st == GP_OK) gpk_co2_trace(s, n, alpha, Kinv, np, D, np, partial, g + p);
@@ -678,9 +749,7 @@ static gp_status predict_core(gp_model *mdl, const double *dXs, int m, int ldxs,
         GP_HIP(ctx, hipMemset2DAsync(Vt + m, (size_t)mp * 8, 0, (size_t)(mp - m) * 8, n, s));
     }
     gp_prof_begin(ctx, GP_PROF_GRAM);
-    if (mdl->kind == 1) gpk_co2_gram(s, dXs, m, mdl->dX, n, mdl->theta.data(), 0, Vt, mp, 0, 1, 0.0);
-    else if (mdl->kind >= 2) gpk_matern_gram_cross(s, dXs, m, ldxs, mdl->dX, n, mdl->ldx, mdl->d, mdl->theta.data(), 2 * mdl->kind - 1, Vt, mp, gp_gram_flag(ctx), mdl->dcen);
-    else gpk_gram_cross(s, dXs, m, ldxs, mdl->dX, n, mdl->ldx, mdl->d, mdl->theta.data(), Vt, mp, gp_gram_flag(ctx), mdl->dcen);
+    gpi_model_gram_cross(mdl, dXs, m, ldxs, Vt, mp);
     gp_prof_end(ctx, GP_PROF_GRAM, 8.0 * m * (double)n + 8.0 * (m + n) * mdl->d);
     // sumsq and the mean accumulate inside the row-panel solves: var = kss - |v|^2, mean = v . (L^-1 y)  (= K* alpha)
     double *dots = partial;
@@ -760,9 +829,7 @@ gp_status gp_predict(gp_model *mdl, const double *Xs, int m, int ldxs, double *m
         // (sn^2 on its diagonal) minus Vt Vt^T on the MFMA syrk, then mirrored on the host copy-out.
         double *dC;
         GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)mp * mp, &dC));
-        if (mdl->kind == 1) gpk_co2_gram(ctx->stream, dXs, m, dXs, m, mdl->theta.data(), 0, dC, mp, 1, 1, 0.0);
-        else if (mdl->kind >= 2) gpk_matern_gram_sym(ctx->stream, dXs, m, d, m, mdl->theta.data(), 2 * mdl->kind - 1, dC, mp, 1, 0.0, gp_gram_flag(ctx));
-        else gpk_gram_sym(ctx->stream, dXs, m, d, m, mdl->theta.data(), dC, mp, 1, 0.0, gp_gram_flag(ctx));
+        gpi_model_gram_sym(mdl, dXs, m, m, dC, mp, 1, 0.0, false);
         gpk_pad_identity(ctx->stream, dC, m, mp, mp);
         gp_prof_begin(ctx, GP_PROF_SYRK);
         gpk_gemm_nt(ctx->stream, mp, mp, mdl->np, -1.0, Vt, mp, Vt, mp, 1.0, dC, mp, 1);

@@ -64,16 +64,7 @@ gp_status gp_fit_co2(gp_ctx *ctx, const double *x, int n, const double *y, const
     if (info) *info = 0;
     GP_REQUIRE(ctx, x && y && theta && n >= 1, "bad arguments");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    gp_model *m = nullptr;
-    GP_TRY(gpi_model_alloc(ctx, n, 1, true, &m));
-    m->kind = 1;
-    gp_status st = gpi_upload_2d(ctx, m->dX, n, x, n, n, 1);
-    if (st == GP_OK) st = gpi_upload_2d(ctx, m->dy, n, y, n, n, 1);
-    if (st == GP_OK) st = gp_model_refit_dev(m, theta, sigma_noise);
-    if (st == GP_OK) st = gp_model_status(m, info);
-    if (st != GP_OK) { gp_model_destroy(m); return st; }
-    *out = m;
-    return GP_OK;
+    return gpi_fit(ctx, 1, x, n, 1, n, y, false, theta, sigma_noise, out, info);
 }
 
 gp_status gp_lml_grad_co2_batched(gp_ctx *ctx, const double *x, int n, const double *y, const double *thetas, int B, int nparams,
@@ -84,47 +75,28 @@ gp_status gp_lml_grad_co2_batched(gp_ctx *ctx, const double *x, int n, const dou
     if (B == 0) return GP_OK;
     GP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    gp_model *m = nullptr;
-    GP_TRY(gpi_model_alloc(ctx, n, 1, true, &m));
-    m->kind = 1;
-    gp_status st = gpi_upload_2d(ctx, m->dX, n, x, n, n, 1);
-    if (st == GP_OK) st = gpi_upload_2d(ctx, m->dy, n, y, n, n, 1);
-    const int np = m->np;
+    const int np = gp_pad(n);
     double *T = nullptr, *Kinv = nullptr, *D = nullptr, *small = nullptr;
-    if (st == GP_OK && nparams > 0) {
-        st = gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)np * np, &T);
-        if (st == GP_OK) st = gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)np * np, &Kinv);
-        if (st == GP_OK) st = gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)np * np, &D);
+    if (nparams > 0) {
+        GP_TRY(gpi_ws_get(ctx, WS_VT, sizeof(double) * (size_t)np * np, &T));
+        GP_TRY(gpi_ws_get(ctx, WS_D, sizeof(double) * (size_t)np * np, &Kinv));
+        GP_TRY(gpi_ws_get(ctx, WS_B, sizeof(double) * (size_t)np * np, &D));
+        GP_TRY(gpi_ws_get(ctx, WS_C, sizeof(double) * ((size_t)2 * np + CO2_P + 2), &small));   // alpha | partial | g[11] | lml
     }
-    if (st == GP_OK) st = gpi_ws_get(ctx, WS_C, sizeof(double) * ((size_t)2 * np + CO2_P + 2), &small);   // alpha | partial | g[11] | lml
-    for (int b = 0; b < B && st == GP_OK; ++b) {
-        const double *th = thetas + (size_t)b * CO2_P;
-        st = gp_model_refit_dev(m, th, sigma_noise);
-        int h = 0;
-        if (st == GP_OK) st = gp_model_status(m, &h);
-        if (info) info[b] = h;
-        if (st == GP_ENOTPD) {   // this setting only: NaN results, go on (lml = NaN there, like gp_lml_grad_rbf_batched)
-            lml[b] = NAN;
-            for (int p = 0; p < nparams; ++p) grad[(size_t)b * nparams + p] = NAN;
-            st = GP_OK;
-            continue;
-        }
-        if (st != GP_OK) break;
-        st = gp_model_get(m, GP_GET_LML, lml + b, 1);
-        if (st != GP_OK || nparams == 0) continue;
+    auto objective = [&](gp_model *m, const double *th, const double **f_dev, const double **g_dev) -> gp_status {
+        *f_dev = m->dlml;
+        if (nparams == 0) return GP_OK;
         double *alpha = small, *partial = small + np, *g = partial + np;
-        st = gpi_model_alpha(m, alpha);
-        if (st != GP_OK) break;
-        gpi_inverse_transpose_lower(ctx, T, m->dL, np, m->ldl, m->ddinv);                       // T = L^-T
-        gpk_gemm_nt(s, np, np, np, 1.0, T, np, T, np, 0.0, Kinv, np, 1, 1);                      // K^-1 = T T^T (lower)
+        GP_TRY(gpi_model_alpha(m, alpha));
+        gpi_model_kinv(m, T, Kinv);
         for (int p = 0; p < nparams; ++p) {                                                    // g_p = 1/2 tr((alpha alpha^T - K^-1) dK/dhp_p)  (:70-78)
             gpk_co2_gram(s, m->dX, n, m->dX, n, th, p + 1, D, np, 1, 0, 0.0);
             gpk_co2_trace(s, n, alpha, Kinv, np, D, np, partial, g + p);
         }
-        st = gpi_download_2d(ctx, grad + (size_t)b * nparams, nparams, g, nparams, nparams, 1);
-    }
-    gp_model_destroy(m);
-    return st;
+        *g_dev = g;
+        return GP_OK;
+    };
+    return gpi_objective_batched(ctx, 1, x, n, 1, n, y, thetas, B, CO2_P, nparams, sigma_noise, lml, grad, info, objective);
 }
 
 gp_status gp_optimize_co2(gp_ctx *ctx, const double *x, int n, const double *y, const double *theta0, int nparams, double sigma_noise,

@@ -56,7 +56,8 @@ struct gp_model {
     int ldl = 0;                     // leading dimension of dL = np + GP_NB: one extra row strip carries y^T through the factorisation
     bool has_x = false;              // false for gp_fit_from_gram
     int kind = 0;                    // kernel the model rebuilds Gram matrices with: 0 = ARD-RBF (theta = d + 2), 1 = Co2Kernel (d = 1, theta = 11),
-                                     // 2 / 3 = ARD Matern 3/2 / 5/2 (theta = d + 2; nu2 = 2 kind - 1)
+                                     // 2 / 3 = ARD Matern 3/2 / 5/2 (theta = d + 2).  The C-ABI and the launchers name the stationary ARD
+                                     // kernels by nu2 = 2 nu instead: 0 = ARD-RBF, 3, 5 (gp_kind_of_nu2 / gp_nu2_of_kind, nowhere else)
     double *dX = nullptr;            // n x d, ld = ldx
     int ldx = 0;                     // leading dimension of dX: n as fitted, the padded size once gp_model_append_dev has made room
     double *dcen = nullptr;          // d: centroid of the rows of dX (centre of the matrix-core Gram forms), set with dX
@@ -76,6 +77,9 @@ struct gp_model {
     double sigma_noise = NAN;
     int last_info = 0;
 };
+inline int gp_kind_of_nu2(int nu2) { return (nu2 + 1) / 2; }
+inline int gp_nu2_of_kind(int kind) { return kind == 0 ? 0 : 2 * kind - 1; }     // not for kind 1: the Co2Kernel has no nu2
+inline bool gp_ard_nu2_ok(int nu2, bool allow_rbf) { return nu2 == 3 || nu2 == 5 || (allow_rbf && nu2 == 0); }
 
 #define GP_SET_ERR(ctx, ...) do { if (ctx) snprintf((ctx)->err, sizeof((ctx)->err), __VA_ARGS__); } while (0)
 #define GP_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -277,6 +281,30 @@ void gpk_model_append(hipStream_t s, const double *Vt, int ldv, const double *Kn
 // dst[j*dst_stride] = src[j*src_stride], j < count
 void gpk_copy_strided(hipStream_t s, double *dst, size_t dst_stride, const double *src, size_t src_stride, int count);
 
+// ---- the stationary ARD kernels by nu2 (0 = ARD-RBF, 3 / 5 = ARD Matern): the one place that picks between the two launcher families.
+// Each forwards to the launcher of the same name without `ard` and does nothing else; a caller that serves one family calls that one.
+inline void gpk_ard_gram_sym(hipStream_t s, int nu2, const double *X, int n, int d, int ldx, const double *theta, double *K, int ldk, int full,
+                             double extra_diag, int *far_flag, const double *center = nullptr) {
+    if (nu2 == 0) gpk_gram_sym(s, X, n, d, ldx, theta, K, ldk, full, extra_diag, far_flag, center);
+    else gpk_matern_gram_sym(s, X, n, d, ldx, theta, nu2, K, ldk, full, extra_diag, far_flag, center);
+}
+inline void gpk_ard_gram_cross(hipStream_t s, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta,
+                               double *Ks, int ldks, int *far_flag, const double *center = nullptr) {
+    if (nu2 == 0) gpk_gram_cross(s, Xs, m, ldxs, X, n, ldx, d, theta, Ks, ldks, far_flag, center);
+    else gpk_matern_gram_cross(s, Xs, m, ldxs, X, n, ldx, d, theta, nu2, Ks, ldks, far_flag, center);
+}
+inline void gpk_ard_far_scan(hipStream_t s, int nu2, const double *Xa, int na, int ldxa, const double *Xb, int nb, int ldxb, int d, const double *theta,
+                             const double *cen, int ldcen, int *far_flag, int epoch) {
+    if (nu2 == 0) gpk_gram_far_scan(s, Xa, na, ldxa, Xb, nb, ldxb, d, theta, cen, ldcen, far_flag, epoch);
+    else gpk_matern_far_scan(s, nu2, Xa, na, ldxa, Xb, nb, ldxb, d, theta, cen, ldcen, far_flag, epoch);
+}
+inline void gpk_ard_lml_grad_traces(hipStream_t s, int nu2, const double *X, int n, int d, int ldx, const double *theta, const double *alpha,
+                                    const double *Kinv, int ldk, double *partials, double *out) {
+    if (nu2 == 0) gpk_lml_grad_traces(s, X, n, d, ldx, theta, alpha, Kinv, ldk, partials, out);
+    else gpk_matern_lml_grad_traces(s, X, n, d, ldx, theta, nu2, alpha, Kinv, ldk, partials, out);
+}
+inline int gpk_ard_trace_partials_size(int nu2, int n, int d) { return nu2 == 0 ? gpk_lml_grad_partials_size(n, d) : gpk_matern_trace_partials_size(d); }
+
 // ---- host-side helpers shared between translation units (defined in gpcore_api.hip) ----
 enum { WS_VT = 0, WS_PARTIAL, WS_SUMSQ, WS_A, WS_B, WS_C, WS_D, WS_E, WS_F, WS_G, WS_H, WS_COUNT };
 gp_status gpi_ws_get(gp_ctx *ctx, int slot, size_t bytes, double **out);
@@ -287,6 +315,30 @@ gp_ctx *gpi_child_ctx(gp_ctx *ctx, int k);
 gp_status gpi_model_alpha(gp_model *m, double *dst);
 const double *gpi_model_alpha_dev(gp_model *m);     // the model's own alpha (n doubles on the device), computed on demand in stream order
 gp_status gpi_model_alloc(gp_ctx *ctx, int n, int d, bool has_x, gp_model **out);
+// The model's kernel (its kind and theta, the Co2Kernel included) on n points X (leading dimension ldx) that need not be its own: K
+// symmetric with extra_diag on the diagonal (lower, or both triangles with full), Ks (m x the model's n) against the training points.
+// own_center: X are the training points, so the matrix-core forms take the model's centroid; else the first point of X.
+void gpi_model_gram_sym(gp_model *m, const double *X, int n, int ldx, double *K, int ldk, int full, double extra_diag, bool own_center);
+void gpi_model_gram_cross(gp_model *m, const double *Xs, int rows, int ldxs, double *Ks, int ldks);
+// T (np x np, ld = np) = L^-T and Kinv (np x np, ld = np) = K^-1 = T T^T, lower triangle, from the factor the model holds
+void gpi_model_kinv(gp_model *m, double *T, double *Kinv);
+// The body of the gp_fit_* entry points, their own argument checks done: a model of `kind` on X (n x d, leading dimension ldx) and y,
+// both on the host or (on_device) both in device memory, fitted at theta.  On failure no model is left and *info is the status read, if any.
+gp_status gpi_fit(gp_ctx *ctx, int kind, const double *X, int n, int d, int ldx, const double *y, bool on_device, const double *theta,
+                  double sigma_noise, gp_model **out, int *info);
+// The bodies of gp_gram_* / gp_cross_gram_* for nu2 = 0 (rbf) and 3, 5 (matern, whose entry points check nu2 first)
+gp_status gpi_gram_dev(gp_ctx *ctx, int nu2, const double *dX, int n, int d, int ldx, const double *theta, double *dK, int ldk, int uplo);
+gp_status gpi_gram_host(gp_ctx *ctx, int nu2, const double *X, int n, int d, int ldx, const double *theta, double *K, int ldk, int uplo);
+gp_status gpi_cross_gram_host(gp_ctx *ctx, int nu2, const double *Xs, int m, int ldxs, const double *X, int n, int ldx, int d, const double *theta,
+                              double *Ks, int ldks);
+// An objective and its gradient at B settings (the rows of thetas, P doubles each) through ONE resident model of `kind` on the host's X
+// and y.  Per setting: refit; a matrix that is not positive definite gives NaN in f[b] and grad[b * nparams ..] and info[b] = its pivot, and
+// the batch goes on; any other failure ends it.  Otherwise objective(m, theta, &f_dev, &g_dev) enqueues its work on the context's stream and
+// names where one double (the value) and nparams doubles (the gradient; not read when nparams == 0) will be on the device; the driver
+// checks the launches and downloads them.  The model is destroyed on every path.
+typedef std::function<gp_status(gp_model *m, const double *theta, const double **f_dev, const double **g_dev)> gpi_objective;
+gp_status gpi_objective_batched(gp_ctx *ctx, int kind, const double *X, int n, int d, int ldx, const double *y, const double *thetas, int B, int P,
+                                int nparams, double sigma_noise, double *f, double *grad, int *info, const gpi_objective &objective);
 // L-BFGS (`history` pairs, at most max_iter iterations, NC batched backtracking steps per iteration, best-seen rule) maximising
 // F over the first nparams entries of theta: the driver behind gp_optimize_rbf and gp_ep_optimize_rbf
 gp_status gpi_lbfgs_maximize(gp_ctx *ctx, int P, int nparams, const double *theta0, int max_iter, int history, int NC,

@@ -43,7 +43,7 @@ gp_status kmm_run(gp_ctx *ctx, int nu2, const double *dXs, int m, int ldxs, cons
 
 gp_status kmm_checks(gp_ctx *ctx, int nu2, const void *Xs, int m, int ldxs, const void *X, int n, int ldx, int d, const void *theta, const void *A, int T,
                      int lda, const void *C, int ldc) {
-    GP_REQUIRE(ctx, nu2 == 0 || nu2 == 3 || nu2 == 5, "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
+    GP_REQUIRE(ctx, gp_ard_nu2_ok(nu2, true), "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
     GP_REQUIRE(ctx, d >= 1 && d <= 64, "bad dimensions (1 <= d <= 64)");
     GP_REQUIRE(ctx, m >= 0 && n >= 0 && T >= 0 && ldxs >= m && ldx >= n && lda >= n && ldc >= m, "bad dimensions (ldxs >= m, ldx >= n, lda >= n, ldc >= m)");
     if (m == 0 || n == 0 || T == 0) return GP_OK;
@@ -108,7 +108,7 @@ gp_status gp_predict_mean_dev(gp_model *mdl, const double *dXs, int m, int ldxs,
         return GP_EINVAL;
     }
     const double *alpha = gpi_model_alpha_dev(mdl);
-    return kmm_run(ctx, mdl->kind == 0 ? 0 : 2 * mdl->kind - 1, dXs, m, ldxs, mdl->dX, mdl->n, mdl->ldx, mdl->d, mdl->theta.data(), mdl->dcen, alpha, 1,
+    return kmm_run(ctx, gp_nu2_of_kind(mdl->kind), dXs, m, ldxs, mdl->dX, mdl->n, mdl->ldx, mdl->d, mdl->theta.data(), mdl->dcen, alpha, 1,
                    mdl->np, dmean, m);
 }
 

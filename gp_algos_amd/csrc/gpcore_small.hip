@@ -286,7 +286,7 @@ gp_status small_alloc(gp_ctx *ctx, int n, int d, int G, int capacity, gp_small *
 
 template <int NU2>
 gp_status small_set_lds_for(gp_ctx *ctx) {
-    const int kind = (NU2 + 1) / 2;
+    const int kind = gp_kind_of_nu2(NU2);
     GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<false, NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 2, kind)));
     GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_posterior_kernel<true, NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, NU2 ? 4 : 3, kind)));
     GP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(small_append_kernel<NU2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds(GP_SMALL_MAX_N, 3, kind)));
@@ -419,10 +419,10 @@ static gp_status small_from_factors(gp_ctx *ctx, const double *X, int n, int d, 
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && G >= 1 && ldx >= n && ldl >= n && std::max(n, capacity) <= GP_SMALL_MAX_N,
                "need 1 <= n <= capacity <= GP_SMALL_MAX_N, 1 <= d <= 64, G >= 1");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    GP_TRY(small_set_lds(ctx, (nu2 + 1) / 2));
+    GP_TRY(small_set_lds(ctx, gp_kind_of_nu2(nu2)));
     gp_small *s = nullptr;
     GP_TRY(small_alloc(ctx, n, d, G, capacity, &s));
-    s->kind = (nu2 + 1) / 2;
+    s->kind = gp_kind_of_nu2(nu2);
     const int cap = s->cap, P = d + 2;
     s->thetas.assign(thetas, thetas + (size_t)G * P);
     gp_status st = gpi_upload_2d(ctx, s->dX, cap, X, ldx, n, d);
@@ -448,10 +448,10 @@ static gp_status small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, 
     GP_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 64 && G >= 1 && ldx >= n && ldy >= n && std::max(n, capacity) <= GP_SMALL_MAX_N,
                "need 1 <= n <= capacity <= GP_SMALL_MAX_N, 1 <= d <= 64, G >= 1");
     GP_HIP(ctx, hipSetDevice(ctx->device));
-    GP_TRY(small_set_lds(ctx, (nu2 + 1) / 2));
+    GP_TRY(small_set_lds(ctx, gp_kind_of_nu2(nu2)));
     gp_small *s = nullptr;
     GP_TRY(small_alloc(ctx, n, d, G, capacity, &s));
-    s->kind = (nu2 + 1) / 2;
+    s->kind = gp_kind_of_nu2(nu2);
     const int cap = s->cap, P = d + 2;
     s->thetas.assign(thetas, thetas + (size_t)G * P);
     s->sigma_noise = sigma_noise;
@@ -464,8 +464,7 @@ static gp_status small_fit(gp_ctx *ctx, const double *X, int n, int d, int ldx, 
     for (int g = 0; g < G && st == GP_OK; ++g) {
         gp_model *m = nullptr;
         int h = 0;
-        if (nu2 == 0) st = gp_fit_rbf_dev(ctx, s->dX, n, d, cap, s->dY + (size_t)g * cap, thetas + (size_t)g * P, sigma_noise, &m, &h);
-        else st = gp_fit_matern_dev(ctx, s->dX, n, d, cap, s->dY + (size_t)g * cap, thetas + (size_t)g * P, nu2, sigma_noise, &m, &h);
+        st = gpi_fit(ctx, s->kind, s->dX, n, d, cap, s->dY + (size_t)g * cap, true, thetas + (size_t)g * P, sigma_noise, &m, &h);
         if (st != GP_OK) { if (info) *info = h; break; }
         gpk_copy_2d(ctx->stream, s->dL + (size_t)g * cap * cap, cap, m->dL, m->ldl, n, n);
         gpk_zero_upper(ctx->stream, s->dL + (size_t)g * cap * cap, n, cap);
@@ -490,7 +489,7 @@ gp_status gp_small_from_factors_matern(gp_ctx *ctx, const double *X, int n, int 
                                        const double *alphas, int nu2, int capacity, gp_small **out) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
-    GP_REQUIRE(ctx, nu2 == 3 || nu2 == 5, "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
+    GP_REQUIRE(ctx, gp_ard_nu2_ok(nu2, false), "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
     return small_from_factors(ctx, X, n, d, ldx, thetas, G, Ls, ldl, alphas, nu2, capacity, out);
 }
 
@@ -503,7 +502,7 @@ gp_status gp_small_fit_matern(gp_ctx *ctx, const double *X, int n, int d, int ld
                               double sigma_noise, int capacity, gp_small **out, int *info) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
-    GP_REQUIRE(ctx, nu2 == 3 || nu2 == 5, "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
+    GP_REQUIRE(ctx, gp_ard_nu2_ok(nu2, false), "nu2 must be 3 (Matern 3/2) or 5 (Matern 5/2)");
     return small_fit(ctx, X, n, d, ldx, Y, ldy, G, thetas, nu2, sigma_noise, capacity, out, info);
 }
 

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void sp_var_rows_kernel(const double *__restri
 }
 
 gp_status syrk_checks(gp_ctx *ctx, int nu2, const void *Z, int M, int ldz, const void *X, int n, int ldx, int d, const void *theta, const void *Phi, int ldphi) {
-    GP_REQUIRE(ctx, nu2 == 0 || nu2 == 3 || nu2 == 5, "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
+    GP_REQUIRE(ctx, gp_ard_nu2_ok(nu2, true), "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
     GP_REQUIRE(ctx, d >= 1 && d <= 64, "bad dimensions (1 <= d <= 64)");
     GP_REQUIRE(ctx, M >= 1 && M <= SP_MAX_M && n >= 1, "bad dimensions (1 <= M <= 8192, n >= 1)");
     GP_REQUIRE(ctx, ldz >= M && ldx >= n && ldphi >= M, "bad dimensions (ldz >= M, ldx >= n, ldphi >= M)");
@@ -140,8 +140,7 @@ gp_status sp_fit(gp_sparse *sp) {
     std::vector<double> th0(sp->theta);
     th0[d + 1] = 0.0;
     gpk_fill(s, sp->dLu, MM, 0.0);
-    if (sp->nu2 == 0) gpk_gram_sym(s, sp->dZ, M, d, M, th0.data(), sp->dLu, Mp, 0, sp->jitter * sf2, gp_gram_flag(ctx), sp->dcen + 64);
-    else gpk_matern_gram_sym(s, sp->dZ, M, d, M, th0.data(), sp->nu2, sp->dLu, Mp, 0, sp->jitter * sf2, gp_gram_flag(ctx), sp->dcen + 64);
+    gpk_ard_gram_sym(s, sp->nu2, sp->dZ, M, d, M, th0.data(), sp->dLu, Mp, 0, sp->jitter * sf2, gp_gram_flag(ctx), sp->dcen + 64);
     GP_TRY(sp_chol(sp, sp->dLu, dinvu, "K(Z, Z) + jitter sf^2 I"));
 
     // T1^T = Lu^-T (upper) into the first half of [T1^T | T2^T]; T1 into W2;  C = (T1 Phi) T1^T, lower, back into Phi's buffer
@@ -227,7 +226,7 @@ gp_status gp_sparse_create(gp_ctx *ctx, int nu2, const double *X, int n, int ldx
                            const double *theta, double jitter, gp_sparse **out) {
     if (!ctx || !out) return GP_EINVAL;
     *out = nullptr;
-    GP_REQUIRE(ctx, nu2 == 0 || nu2 == 3 || nu2 == 5, "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
+    GP_REQUIRE(ctx, gp_ard_nu2_ok(nu2, true), "nu2 must be 0 (ARD-RBF), 3 (Matern 3/2) or 5 (Matern 5/2)");
     GP_REQUIRE(ctx, d >= 1 && d <= 64, "bad dimensions (1 <= d <= 64)");
     GP_REQUIRE(ctx, M >= 1 && M <= SP_MAX_M && n >= 1, "bad dimensions (1 <= M <= 8192, n >= 1)");
     GP_REQUIRE(ctx, ldx >= n && ldz >= M, "bad dimensions (ldx >= n, ldz >= M)");

@@ -5,7 +5,7 @@
 //   trsm_panel_upper : X <- X * U^-T for the backSolve(R, B) entry point    (MatrixUtils.scala:33-35)
 //   transpose, identity, panel gemv helpers
 // The O(n^3) work lives in kernels_gemm.hip, the critical-path diagonal-block kernels in kernels_diag.hip.
-#include "gpcore_internal.h"
+#include "ard_tile.h"
 
 namespace {
 
@@ -180,14 +180,6 @@ __global__ void set_identity_upper_kernel(double *A, int n, int lda) {
 constexpr int TR_T = 64, TR_DC = 8, TR_DMAX = 64;
 struct TraceParams { double inv_ls2[TR_DMAX]; };
 
-__device__ __forceinline__ void tile_lower_tr(int t, int &bi, int &bj) {
-    int b = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (b * (b + 1) / 2 > t) --b;
-    while ((b + 1) * (b + 2) / 2 <= t) ++b;
-    bi = b;
-    bj = t - b * (b + 1) / 2;
-}
-
 __device__ __forceinline__ double block_sum_256(double v, double *red) {
     red[threadIdx.x] = v;
     __syncthreads();
@@ -224,7 +216,7 @@ __global__ __launch_bounds__(256) void lml_grad_trace_kernel(const double *__res
     }
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int bi, bj;
-        tile_lower_tr(t, bi, bj);
+        gp_tile_lower(t, bi, bj);
         const int gi = bi * TR_T + ti;
         const double wgt = (bi == bj) ? 1.0 : 2.0;
         __syncthreads();
@@ -322,7 +314,7 @@ __global__ __launch_bounds__(256) void lml_grad_trace8_kernel(const double *__re
     for (int k = 0; k < TR_DC; ++k) sk[k] = 0.0;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int bi, bj;
-        tile_lower_tr(t, bi, bj);
+        gp_tile_lower(t, bi, bj);
         const int gi = bi * TR_T + ti;
         const double wgt = (bi == bj) ? 1.0 : 2.0;
         __syncthreads();

@@ -8,7 +8,7 @@
 // tile: each thread owns one row point (its d features live in registers) and 16 column points
 // (read as LDS broadcasts).  The symmetric builder evaluates tiles on/below the diagonal only, like
 // the reference's j <= i loop, and mirrors through an LDS transpose so both stores are coalesced.
-#include "gpcore_internal.h"
+#include "ard_tile.h"
 #include <atomic>
 
 namespace {
@@ -28,14 +28,6 @@ struct GramParams {
     double lnsf2;   // ln(sf^2): the unit kernel carries it inside the exponent
 };
 
-__device__ __forceinline__ void tile_lower(int t, int &bi, int &bj) {
-    int b = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (b * (b + 1) / 2 > t) --b;
-    while ((b + 1) * (b + 2) / 2 <= t) ++b;
-    bi = b;
-    bj = t - b * (b + 1) / 2;
-}
-
 template <bool SYM, bool DER = false>
 __global__ __launch_bounds__(256) void gram_rbf_kernel(const double *__restrict__ Xr, int nr, int ldxr,
                                                        const double *__restrict__ Xc, int nc, int ldxc, int d,
@@ -46,7 +38,7 @@ __global__ __launch_bounds__(256) void gram_rbf_kernel(const double *__restrict_
     __shared__ double xcs[DC][GT];
     __shared__ double tile[SYM ? GT * (GT + 1) : 1];
     int bi, bj;
-    if (SYM) tile_lower(blockIdx.x, bi, bj);
+    if (SYM) gp_tile_lower(blockIdx.x, bi, bj);
     else { bi = blockIdx.x % nbr; bj = blockIdx.x / nbr; }
     const int tid = threadIdx.x, ti = tid & 63, tq = tid >> 6;
     const int gi = bi * GT + ti;
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const double *__restrict
     __shared__ double nrm[2][GT];
     __shared__ double tile[SYM ? GT * (GT + 1) : 1];
     int bi, bj;
-    if (SYM) tile_lower(blockIdx.x, bi, bj);
+    if (SYM) gp_tile_lower(blockIdx.x, bi, bj);
     else { bi = blockIdx.x % nbr; bj = blockIdx.x / nbr; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const int i0 = bi * GT, j0 = bj * GT;

@@ -32,7 +32,8 @@
 //     them would not fit beside d = 64 features): its loads are issued at the top of the chunk and written after the epilogue, so
 //     there is a second barrier per chunk.  The four waves' tiles are added in wave order through the same buffer.
 // Rows past m and training points past n are clamped to the last point, computed and never stored (matern_mfma_kernel).
-#include "gpcore_internal.h"
+#include "ard_tile.h"
+#include <algorithm>
 
 namespace {
 
@@ -42,24 +43,8 @@ constexpr int KAS = 66;       // LDS row stride of the image of A
 constexpr int KDMAX = 64;
 constexpr int KPQ = KDMAX / 4;        // features a thread stages at most (point = lane, feature = wave + 4 q)
 
-struct KmmParams {
-    double scale[KDMAX];       // matrix-core form: 1 / l_k; per-pair form: 1 / l_k^2; zero beyond d
-};
-
 typedef double kmm_d4 __attribute__((ext_vector_type(4)));
 #define KMM_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
-// k / sf^2 from r^2
-template <int NU2>
-__device__ __forceinline__ double kmm_value(double r2) {
-    if constexpr (NU2 == 0) {
-        return exp(-0.5 * r2);
-    } else {
-        double k0, h;
-        matern_terms<NU2>(r2, k0, h);
-        return k0;
-    }
-}
 
 constexpr int kmm_a_doubles(int NT) { return NT == 0 ? 2 * KM + 4 * KM : 16 * NT * KAS; }     // NT = 0: alpha x 2 buffers, then the waves' sums
 size_t kmm_lds_bytes(int d, int NT) { return sizeof(double) * ((size_t)3 * ((d + 3) & ~3) * KZS + 2 * KDMAX + kmm_a_doubles(NT)); }
@@ -67,7 +52,7 @@ size_t kmm_lds_bytes(int d, int NT) { return sizeof(double) * ((size_t)3 * ((d +
 // part[((z * T) + t) * pm + i]: the sum over this workgroup's training range for test point i and column t of A, without sf^2
 template <int NU2, bool PAIR, int NT>
 __global__ __launch_bounds__(256) void kmm_kernel(const double *__restrict__ Xs, int m, int ldxs, const double *__restrict__ X, int n, int ldx, int d,
-                                                  KmmParams prm, const double *__restrict__ center, const double *__restrict__ A, int T, int lda,
+                                                  ArdScale prm, const double *__restrict__ center, const double *__restrict__ A, int T, int lda,
                                                   int per, double *__restrict__ part, int pm, const int *__restrict__ far_flag, int epoch) {
     // the two halves behind one scan: the one that is not needed returns at its first instruction
     if (PAIR ? (far_flag && *far_flag != epoch) : (*far_flag == epoch)) return;
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(256) void kmm_kernel(const double *__restrict__ Xs,
 #pragma unroll
         for (int it = 0; it < 4; ++it)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[it][r] = kmm_value<NU2>(PAIR ? acc[it][r] : fmax(-2.0 * acc[it][r], 0.0));
+            for (int r = 0; r < 4; ++r) acc[it][r] = ard_value<NU2>(PAIR ? acc[it][r] : fmax(-2.0 * acc[it][r], 0.0));
         // second product
         if (NT == 0) {
             const double *al = as + (c & 1) * KM + 16 * wave + fk;
@@ -289,7 +274,7 @@ struct KmmArgs {
     hipStream_t s;
     const double *Xs, *X, *center, *A;
     int m, ldxs, n, ldx, d, T, lda, per, nz, pm, gy;
-    KmmParams inv_ls, inv_ls2;
+    ArdScale inv_ls, inv_ls2;
     double *part;
     int *far_flag;
     int epoch;
@@ -337,23 +322,10 @@ void gpk_kernel_matmul(hipStream_t s, int nu2, const double *Xs, int m, int ldxs
     a.s = s, a.Xs = Xs, a.X = X, a.center = center, a.A = A, a.part = partials;
     a.m = m, a.ldxs = ldxs, a.n = n, a.ldx = ldx, a.d = d, a.T = T, a.lda = lda;
     kmm_split(m, n, T, &a.per, &a.nz, &a.pm, &a.gy);
-    for (int k = 0; k < KDMAX; ++k) a.inv_ls.scale[k] = a.inv_ls2.scale[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        a.inv_ls.scale[k] = 1.0 / fabs(theta[1 + k]);
-        a.inv_ls2.scale[k] = 1.0 / (theta[1 + k] * theta[1 + k]);
-    }
-    const double sf2 = theta[0] * theta[0];
-    // the matrix-core form wants a centre, a finite non-zero amplitude and leading dimensions below 2^25, as the Gram builders' does
-    const bool mfma_ok = far_flag && center && std::isfinite(sf2) && sf2 != 0.0 && ldxs < (1 << 25) && ldx < (1 << 25) && lda < (1 << 25);
-    a.far_flag = mfma_ok ? far_flag : nullptr;
-    a.epoch = 0;
-    if (mfma_ok) {
-        a.epoch = gpk_gram_epoch();
-        if (nu2 == 0) gpk_gram_far_scan(s, Xs, m, ldxs, X, n, ldx, d, theta, center, 1, far_flag, a.epoch);
-        else gpk_matern_far_scan(s, nu2, Xs, m, ldxs, X, n, ldx, d, theta, center, 1, far_flag, a.epoch);
-    }
+    ard_scales(theta, d, &a.inv_ls, &a.inv_ls2);
+    a.far_flag = ard_far_scan_or_pair(s, nu2, Xs, m, ldxs, X, n, ldx, d, theta, center, std::max({ldxs, ldx, lda}), far_flag, &a.epoch);
     if (nu2 == 0) kmm_tiles_dispatch<0>(a);
     else if (nu2 == 3) kmm_tiles_dispatch<3>(a);
     else kmm_tiles_dispatch<5>(a);
-    hipLaunchKernelGGL(kmm_finish_kernel, dim3((m + 255) / 256, std::min(T, 4096)), dim3(256), 0, s, partials, a.pm, a.nz, m, T, sf2, C, ldc);
+    hipLaunchKernelGGL(kmm_finish_kernel, dim3((m + 255) / 256, std::min(T, 4096)), dim3(256), 0, s, partials, a.pm, a.nz, m, T, theta[0] * theta[0], C, ldc);
 }

@@ -38,7 +38,8 @@
 //              d = 64: 144 + 8 + 3 = 155 KiB of the CU's 160.
 // Rows past M and observations past n are clamped to the last point; such rows are computed and never read back, such observations
 // contribute zero.  The caller's arrays are never padded.
-#include "gpcore_internal.h"
+#include "ard_tile.h"
+#include <algorithm>
 
 namespace {
 
@@ -46,23 +47,8 @@ constexpr int ST = 128;         // tile edge of Phi
 constexpr int SZS = 144;        // LDS row stride of an inducing-point block
 constexpr int SDMAX = 64;
 
-struct KsParams {
-    double scale[SDMAX];        // matrix-core form: 1 / l_k; per-pair form: 1 / l_k^2; zero beyond d
-};
-
 typedef double ks_d4 __attribute__((ext_vector_type(4)));
 #define KS_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
-template <int NU2>
-__device__ __forceinline__ double ks_value(double r2) {
-    if constexpr (NU2 == 0) {
-        return exp(-0.5 * r2);
-    } else {
-        double k0, h;
-        matern_terms<NU2>(r2, k0, h);
-        return k0;
-    }
-}
 
 constexpr int ks_stride(int KC) { return KC == 64 ? 80 : 16; }
 constexpr int ks_bufs(int KC) { return KC == 64 ? 2 : 1; }
@@ -76,7 +62,7 @@ int ks_tiles(int M) { const int nb = (M + ST - 1) / ST; return nb * (nb + 1) / 2
 // upart[z * up + a]: the same for u, without sf^2 (up = 128 * tile rows)
 template <int NU2, bool PAIR, int KC>
 __global__ __launch_bounds__(256) void ksyrk_kernel(const double *__restrict__ Z, int M, int ldz, const double *__restrict__ X, int n, int ldx, int d,
-                                                    KsParams prm, const double *__restrict__ center, const double *__restrict__ y, int per,
+                                                    ArdScale prm, const double *__restrict__ center, const double *__restrict__ y, int per,
                                                     double *__restrict__ part, double *__restrict__ upart, int up, const int *__restrict__ far_flag, int epoch) {
     // the two halves behind one scan: the one that is not needed returns at its first instruction
     if (PAIR ? (far_flag && *far_flag != epoch) : (*far_flag == epoch)) return;
@@ -92,12 +78,9 @@ __global__ __launch_bounds__(256) void ksyrk_kernel(const double *__restrict__ Z
     double *ys = nrm + 2 * ST;                   // NB x KC
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const int wr = wave >> 1, wc = wave & 1;
-    // tile t of the row-major lower order: bi (bi + 1) / 2 + bj
     const int t = blockIdx.x;
-    int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (bi * (bi + 1) / 2 > t) --bi;
-    while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
-    const int bj = t - bi * (bi + 1) / 2;
+    int bi, bj;
+    gp_tile_lower(t, bi, bj);
     const bool diag = bi == bj, same = diag && wr == wc, idle = diag && wr < wc;
     const bool do_u = y != nullptr && bj == 0 && wc == 0;
     const int jlo = blockIdx.z * per * KC, jhi = min(n, jlo + per * KC), nchunks = (jhi - jlo + KC - 1) / KC;
@@ -225,12 +208,12 @@ __global__ __launch_bounds__(256) void ksyrk_kernel(const double *__restrict__ Z
 #pragma unroll
                 for (int it = 0; it < 4; ++it)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pr[it][r] = ks_value<NU2>(PAIR ? pr[it][r] : fmax(-2.0 * pr[it][r], 0.0));
+                    for (int r = 0; r < 4; ++r) pr[it][r] = ard_value<NU2>(PAIR ? pr[it][r] : fmax(-2.0 * pr[it][r], 0.0));
                 if (!same) {
 #pragma unroll
                     for (int it = 0; it < 4; ++it)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) pc[it][r] = ks_value<NU2>(PAIR ? pc[it][r] : fmax(-2.0 * pc[it][r], 0.0));
+                        for (int r = 0; r < 4; ++r) pc[it][r] = ard_value<NU2>(PAIR ? pc[it][r] : fmax(-2.0 * pc[it][r], 0.0));
                 }
                 if (left - 16 * sl < 16) {       // the range ends inside these 16 observations: the clamped ones leave through a zero row operand
 #pragma unroll
@@ -300,10 +283,8 @@ __global__ __launch_bounds__(256) void ksyrk_kernel(const double *__restrict__ Z
 __global__ __launch_bounds__(256) void ksyrk_finish_kernel(const double *__restrict__ part, int ntiles, int nz, int M, double sf4, double *__restrict__ Phi,
                                                            int ldphi) {
     const int t = blockIdx.x;
-    int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (bi * (bi + 1) / 2 > t) --bi;
-    while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
-    const int bj = t - bi * (bi + 1) / 2;
+    int bi, bj;
+    gp_tile_lower(t, bi, bj);
     const int e = blockIdx.y * 256 + threadIdx.x, a = bi * ST + e / ST, b = bj * ST + e % ST;
     if (a >= M || b > a) return;
     double acc = 0.0;
@@ -338,7 +319,7 @@ struct KsArgs {
     hipStream_t s;
     const double *Z, *X, *center, *y;
     int M, ldz, n, ldx, d, per, nz, up;
-    KsParams inv_ls, inv_ls2;
+    ArdScale inv_ls, inv_ls2;
     double *part, *upart;
     int epoch;
 };
@@ -386,21 +367,9 @@ void gpk_kernel_syrk(hipStream_t s, int nu2, const double *Z, int M, int ldz, co
     a.up = (M + ST - 1) / ST * ST;
     a.part = partials;
     a.upart = partials + (size_t)a.nz * tiles * ST * ST;
-    for (int k = 0; k < SDMAX; ++k) a.inv_ls.scale[k] = a.inv_ls2.scale[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        a.inv_ls.scale[k] = 1.0 / fabs(theta[1 + k]);
-        a.inv_ls2.scale[k] = 1.0 / (theta[1 + k] * theta[1 + k]);
-    }
+    ard_scales(theta, d, &a.inv_ls, &a.inv_ls2);
     const double sf2 = theta[0] * theta[0];
-    // the matrix-core form wants a centre, a finite non-zero amplitude and leading dimensions below 2^25, as the Gram builders' does
-    const bool mfma_ok = far_flag && center && std::isfinite(sf2) && sf2 != 0.0 && ldz < (1 << 25) && ldx < (1 << 25);
-    a.epoch = 0;
-    if (mfma_ok) {
-        a.epoch = gpk_gram_epoch();
-        if (nu2 == 0) gpk_gram_far_scan(s, Z, M, ldz, X, n, ldx, d, theta, center, 1, far_flag, a.epoch);
-        else gpk_matern_far_scan(s, nu2, Z, M, ldz, X, n, ldx, d, theta, center, 1, far_flag, a.epoch);
-    }
-    int *flag = mfma_ok ? far_flag : nullptr;
+    int *flag = ard_far_scan_or_pair(s, nu2, Z, M, ldz, X, n, ldx, d, theta, center, std::max(ldz, ldx), far_flag, &a.epoch);
     if (nu2 == 0) ks_dispatch<0>(a, flag);
     else if (nu2 == 3) ks_dispatch<3>(a, flag);
     else ks_dispatch<5>(a, flag);

@@ -11,19 +11,11 @@
 //   loo_mirror_scale_kernel  K^-1 mirrored into its upper triangle in place, and K^-1 diag(c) written beside it: the GEMM's two operands
 //   loo_weight_kernel        Q2 <- Q2 - alpha b^T - b alpha^T on the lower triangle, in place
 // Every kernel is a plain grid; every sum has a fixed order (no atomics): the same inputs give the same bits.
-#include "gpcore_internal.h"
+#include "ard_tile.h"
 
 namespace {
 
 constexpr int LT = 64;        // tile edge of the n^2 passes
-
-__device__ __forceinline__ void loo_tile_lower(int t, int &bi, int &bj) {
-    int b = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (b * (b + 1) / 2 > t) --b;
-    while ((b + 1) * (b + 2) / 2 <= t) ++b;
-    bi = b;
-    bj = t - b * (b + 1) / 2;
-}
 
 // partial[chunk][i] = sum over the chunk's columns j >= i of T(i, j)^2, T = L^-T upper triangular, np x np column-major (ld = np).
 // A workgroup owns 64 rows (lane = row: a column's 64 entries are one 512-byte read) and the columns [chunk * per, (chunk + 1) * per) from
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(256) void loo_symv_sum_kernel(const double *__restr
 __global__ __launch_bounds__(256) void loo_mirror_scale_kernel(double *__restrict__ A, int ld, const double *__restrict__ c, double *__restrict__ S) {
     __shared__ double tile[LT * (LT + 1)];
     int bi, bj;
-    loo_tile_lower(blockIdx.x, bi, bj);
+    gp_tile_lower(blockIdx.x, bi, bj);
     const int ti = threadIdx.x & 63, tq = threadIdx.x >> 6, i0 = bi * LT, j0 = bj * LT;
     const bool diag = bi == bj;
 #pragma unroll
@@ -173,7 +165,7 @@ __global__ __launch_bounds__(256) void loo_mirror_scale_kernel(double *__restric
 // Q(i, j) -= alpha_i b_j + b_i alpha_j for n > i >= j: the rank-2 term on the triangle the trace kernels read
 __global__ __launch_bounds__(256) void loo_weight_kernel(double *__restrict__ Q, int ld, int n, const double *__restrict__ alpha, const double *__restrict__ b) {
     int bi, bj;
-    loo_tile_lower(blockIdx.x, bi, bj);
+    gp_tile_lower(blockIdx.x, bi, bj);
     const int ti = threadIdx.x & 63, tq = threadIdx.x >> 6, i = bi * LT + ti;
     if (i >= n) return;
     const double ai = alpha[i], bv = b[i];

@@ -27,7 +27,7 @@
 //
 // matern_trace_kernel: all P = d + 2 sums of the LML gradient 1/2 tr((alpha alpha^T - K^-1) dK / d theta_p) in one pass over the lower
 // triangle of W = alpha alpha^T - K^-1; k and h are recomputed from X tiles, no derivative matrix exists anywhere.
-#include "gpcore_internal.h"
+#include "ard_tile.h"
 
 namespace {
 
@@ -45,14 +45,6 @@ struct MaternParams {
 };
 
 typedef double matern_d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void matern_tile_lower(int t, int &bi, int &bj) {
-    int b = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (b * (b + 1) / 2 > t) --b;
-    while ((b + 1) * (b + 2) / 2 <= t) ++b;
-    bi = b;
-    bj = t - b * (b + 1) / 2;
-}
 
 // (matern_terms: k / sf^2 and h from r^2, gpcore_internal.h -- kernels_kmm.hip evaluates the same kernels)
 
@@ -84,7 +76,7 @@ __global__ __launch_bounds__(256) void matern_mfma_kernel(const double *__restri
     __shared__ double nrm[2][MT];
     __shared__ double tile[MODE == 2 ? MT * (MT + 1) : 1];
     int bi, bj;
-    if (SYM) matern_tile_lower(blockIdx.x, bi, bj);
+    if (SYM) gp_tile_lower(blockIdx.x, bi, bj);
     else { bi = blockIdx.x % nbr; bj = blockIdx.x / nbr; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const int i0 = bi * MT, j0 = bj * MT;
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(256) void matern_pair_kernel(const double *__restri
     __shared__ double xcs[MDC][MT];
     __shared__ double tile[SYM ? MT * (MT + 1) : 1];
     int bi, bj;
-    if (SYM) matern_tile_lower(blockIdx.x, bi, bj);
+    if (SYM) gp_tile_lower(blockIdx.x, bi, bj);
     else { bi = blockIdx.x % nbr; bj = blockIdx.x / nbr; }
     const int tid = threadIdx.x, ti = tid & 63, tq = tid >> 6;
     const int gi = bi * MT + ti;
@@ -271,7 +263,7 @@ __global__ __launch_bounds__(256) void matern_trace_kernel(const double *__restr
     for (int kk = 0; kk < MDC; ++kk) sk[kk] = 0.0;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         int bi, bj;
-        matern_tile_lower(t, bi, bj);
+        gp_tile_lower(t, bi, bj);
         const int gi = bi * MT + ti;
         const double wgt = (bi == bj) ? 1.0 : 2.0;
         __syncthreads();

@@ -136,6 +136,13 @@ def test_boundary_argument_errors(ctx):
     # m = 0 is a no-op
     assert ctx._lib.gp_posterior_from_factor(ctx.h, L.dptr(p["X"]), 30, 2, 30, L.dptr(L.f64(p["theta"])), L.dptr(Lo), 30, L.dptr(ao),
                                              L.dptr(L.f64(p["Xs"])), 0, 1, L.dptr(mean), None, None, 1, None, 30) == L.GP_OK
+    # a rejected fit leaves no model and a zeroed status, whatever the caller's info held: gp_fit_rbf_dev with ldx < n
+    import ctypes as C
+    dX, dy = ctx.upload(p["X"]), ctx.upload(p["y"])
+    h, info = C.c_void_p(1), C.c_int(-77)
+    st = ctx._lib.gp_fit_rbf_dev(ctx.h, dX, 30, 2, 29, dy, L.dptr(L.f64(p["theta"])), float("nan"), C.byref(h), C.byref(info))
+    ctx.dev_free(dX), ctx.dev_free(dy)
+    assert st == L.GP_EINVAL and h.value is None and info.value == 0
 
 
 def test_mirror_compute_posterior_both_kernel_routes(ctx):
